@@ -11,12 +11,17 @@ already resident in HBM, through the HIP library's C ABI.
          (admm_deconv.parallel.ShardGather).  `python bench.py --gpus N` spawns the N ranks itself; the
          driver's `torchrun --nproc-per-node N bench.py --gpus N` sets RANK/WORLD_SIZE and is used as is.
 
-Prints ONE JSON line on rank 0.  Besides the driver's keys it carries
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes the outputs of the
+last timed step when --dump-outputs is given, and prints the line (metric, value, ms_per_step, ...).  With
+--full the line also carries, from runs of their own after the timed steps,
+  kernels       -- per-kernel-class launch counts and hipEvent durations of an instrumented solve / step.
   roofline      -- dominant kernel: algorithmic bytes per launch / measured avg launch duration
                    (hipEvents on the launch stream, via the library profiler) vs 8 TB/s HBM peak;
                    `traffic` = PMC-measured HBM bytes per launch from profiles/ when available.
   cpu_baseline  -- the C restatement of the reference CPU solve (oracle/admm_oracle.c, fp32, OpenMP)
                    timed on this host on a bounded sample of the same workload (rank 0, N = 1 only).
+  ranks, solve_only -- N > 1: per-rank diagnostics, the same steps without the gather, and (--gather-engine
+                   both) the same steps gathered by the other engine.
 """
 from __future__ import annotations
 
@@ -85,6 +90,13 @@ def parse():
                     "launched by torchrun")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures: per-kernel timing "
+                         "and roofline, the CPU baseline, and on N > 1 the solve-only and other-gather-engine legs "
+                         "with the per-rank diagnostics (off by default: a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32; a "
+                         "fixed seeded sample of the planes of an output larger than the size limit)")
     ap.add_argument("--config", default=None, choices=sorted(synth.CONFIGS),
                     help="default: c2 on one GPU, c3 (2048 global, sharded + gathered) on N > 1")
     ap.add_argument("--batch", type=int, default=None, help="images per GPU (default: the config's; c3 -> 2048/N)")
@@ -93,13 +105,13 @@ def parse():
     ap.add_argument("--gather-engine", default="both", choices=("both", "ipc", "rccl"),
                     help="N > 1: 'ipc' = every rank copies its solved slices into rank 0's IPC-shared receive buffer "
                          "(async peer copies, SDMA: no CU held); 'rccl' = dist.gather over RCCL (falls back to it "
-                         "when the IPC handle cannot be opened); 'both' (default) = the metric with ipc, plus the "
-                         "same steps with rccl timed in the same invocation (per-rank diagnostics)")
+                         "when the IPC handle cannot be opened); 'both' (default) = the metric with ipc, plus, with "
+                         "--full, the same steps with rccl timed in the same invocation (per-rank diagnostics)")
     ap.add_argument("--backend", default="nccl", choices=("nccl", "gloo"),
                     help="N > 1: nccl (RCCL over xGMI); gloo only to rehearse the schedule with ranks sharing a GPU")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="library option (admm_set_option), e.g. FUSED=0 or LINE_T=4; experiments only")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU-baseline sample duration")
     ap.add_argument("--distinct", type=int, default=64, help="distinct synthetic images generated per rank (tiled)")
     ap.add_argument("--serial-branches", action="store_true",
@@ -117,6 +129,28 @@ def parse():
                          "per step make the step launch-bound (profiles/r05_c5_small_batch_graph.jsonl); off above")
     ap.add_argument("--no-graph", dest="graph", action="store_false")
     return ap.parse_args()
+
+
+DUMP_BYTES = 48 << 20   # all files of one --dump-outputs together stay below 64 MB
+
+
+def dump_outputs(dirname, tensors):
+    """--dump-outputs: write each tensor of {name: tensor} as dirname/name.npy (float32, or float64 where it is).
+    Every tensor gets an equal share of DUMP_BYTES; of a larger one a fixed sample of its planes (the last two
+    dimensions) is written, drawn by a generator seeded with 0, in ascending plane order: the same planes in
+    every run of the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    budget = DUMP_BYTES // len(tensors)
+    for name, t in tensors.items():
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float()
+        if t.numel() * t.element_size() > budget:
+            planes = t.reshape(-1, *t.shape[-2:])
+            n = budget // (planes[0].numel() * t.element_size())
+            idx = np.sort(np.random.default_rng(0).choice(planes.shape[0], n, replace=False))
+            t = planes[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy())
 
 
 def make_inputs(cfg, B, g0, distinct, dev):
@@ -169,6 +203,8 @@ def bench_c5(args, dev):
     net = layers.Parallel(layers.chcat, *branch, streams=not args.serial_branches,   # net_build.jl:121-125
                           merge=False if (args.no_merge or args.serial_branches) else ("always" if args.merge_iso else True))
     merged = net._mergeable(x)
+    # --dump-outputs: the tensors of the last step (of a replayed graph: its static tensors, rewritten by every replay)
+    kept = {} if args.dump_outputs else None
 
     def step():
         out = net(x)                                          # 5 branches on their own HIP streams, chcat
@@ -178,6 +214,8 @@ def bench_c5(args, dev):
             for L in branch:
                 L.lam -= 1e-3 * L.lam.grad
                 L.lam.grad = None
+        if kept is not None:
+            kept["out"], kept["loss"] = out, loss
         return loss
 
     run = step
@@ -212,6 +250,30 @@ def bench_c5(args, dev):
         run()
     torch.cuda.synchronize(dev)
     el = time.perf_counter() - t0
+    if kept is not None:
+        # the layer outputs (chcat of the 5 branches), the loss, and the trained lambdas after the last update
+        dump_outputs(args.dump_outputs, {"out": kept["out"], "loss": kept["loss"],
+                                         "lam": torch.cat([L.lam.detach().reshape(-1) for L in branch])})
+        kept = None
+    roof, kernels = c5_profile(args, net, step, branch, merged, B, M, N, P, K) if args.full else (None, None)
+    line = {
+        "metric": "c5 ADMM denoiser-branch train step (fwd + adjoint) images/s", "value": round(B * args.steps / el, 2),
+        "unit": "images/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1000 * el / args.steps, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"c5: batch {B} of {M}x{N}x{P}, 5 x ADMMDeconvF2((), {K}, rho, relu1) + chcat, "
+                               "GMSD loss (HIP), backward through the recorded adjoint "
+                               f"({'iso' if args.iso else 'aniso'}; "
+                               f"{'branches in one grid' if merged else 'per-branch solves'}"
+                               f"{'; whole step replayed as one HIP graph' if graph is not None else ''})",
+                   "global_batch": B}}
+    if args.full:
+        line.update(roofline=roof, kernels=kernels)
+    print(json.dumps(line))
+
+
+def c5_profile(args, net, step, branch, merged, B, M, N, P, K):
+    """--full, c5: (roofline, kernels) of the step that bench_c5 timed."""
     # per-kernel timing from a separate instrumented step with the branches serialised, so that each
     # launch's hipEvent duration is its own (concurrent branches share the CUs)
     net.use_streams = False
@@ -328,18 +390,7 @@ def bench_c5(args, dev):
         roof = {"bound": "hbm", "kernel": "adjoint (line_adj)", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS,
                 "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
                 "algorithmic_bytes_per_launch": per_launch, "avg_launch_ms": round(a["avg_ms"], 5)}
-    print(json.dumps({
-        "metric": "c5 ADMM denoiser-branch train step (fwd + adjoint) images/s", "value": round(B * args.steps / el, 2),
-        "unit": "images/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1000 * el / args.steps, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"c5: batch {B} of {M}x{N}x{P}, 5 x ADMMDeconvF2((), {K}, rho, relu1) + chcat, "
-                               "GMSD loss (HIP), backward through the recorded adjoint "
-                               f"({'iso' if args.iso else 'aniso'}; "
-                               f"{'branches in one grid' if merged else 'per-branch solves'}"
-                               f"{'; whole step replayed as one HIP graph' if graph is not None else ''})",
-                   "global_batch": B},
-        "roofline": roof, "kernels": kernels}))
+    return roof, kernels
 
 
 def cpu_baseline(cfg, psf, base, target_s):
@@ -419,6 +470,69 @@ def spawn_ranks(n):
     rcs = [p.wait() for p in procs]
     bad = [rc for rc in rcs if rc != 0]
     sys.exit(bad[0] if bad else 0)
+
+
+def kernels_roofline(config, cfg, B, y, h, out, ws, stream, ms_per_step):
+    """--full: (kernels, roofline) of the solve that main() timed at ms_per_step."""
+    M, N, P, K = cfg["M"], cfg["N"], cfg["P"], cfg["K"]
+    # ---- per-kernel timing (separate instrumented solve; not part of the timed region) ----
+    _lib.profile_reset()
+    _lib.profile_enable(True)
+    reps = 2
+    for _ in range(reps):
+        admm_deconv.tvd_fft(y, synth.LAMBDA, synth.RHO, h, False, K, out=out, workspace=ws, stream=stream)
+    _lib.profile_enable(False)
+    planes = B * P
+    # planes per launch: the MALL-resident schedule runs large 2-pass batches as chunks on several streams
+    chunk, nstreams = _lib.forward_schedule(M, N, False, cfg["psf"][0], planes)
+    kb = kernel_bytes_per_plane(M, N, K)
+    kernels = {}
+    for cls, name in _lib.KERNEL_CLASSES.items():
+        ms, n = _lib.profile_get(cls)
+        if n == 0:
+            continue
+        avg_ms = ms / n
+        e = {"launches_per_solve": n // reps, "avg_ms": avg_ms, "total_ms_per_solve": ms / reps}
+        if name in kb:
+            e["algorithmic_bytes_per_launch"] = kb[name] * chunk
+            e["achieved_GBps"] = kb[name] * chunk / (avg_ms * 1e-3) / 1e9
+        kernels[name] = e
+    dom = max((k for k in kernels if k in kb), key=lambda k: kernels[k]["total_ms_per_solve"])
+    alg_bytes = kb["plane"] * planes if "plane" in kernels else canonical_bytes(M, N, K) * planes
+    traffic = load_traffic(config, dom, planes=chunk)
+    ach = kernels[dom]["achieved_GBps"]
+    roofline = {
+        "bound": "hbm", "kernel": dom, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic,
+        # against the measured streaming ceiling of the same read/write mix (not the 8 TB/s spec)
+        "achievable_peak": achievable_gbs(),
+        "frac_of_achievable": round(ach / achievable_gbs(), 4) if achievable_gbs() else None,
+        "algorithmic_bytes_per_launch": kernels[dom]["algorithmic_bytes_per_launch"],
+        "avg_launch_ms": round(kernels[dom]["avg_ms"], 5),
+        "compute": compute_side(config, dom, kernels[dom]["avg_ms"], chunk),
+        # launches of `chunk_planes` planes; with streams > 1 that many chunks' launches run concurrently, so a
+        # launch's duration includes its share of the chip (the whole-solve figure below is the aggregate)
+        # (rocprofv3's begin -> end of the same launches is shorter: profiles/r06_c4_mall_kernel_stats.csv, DESIGN.md
+        # s5); overlap = the kernels' event time per solve over the solve's wall time
+        "schedule": {"chunk_planes": chunk, "streams": nstreams,
+                     "overlap": round(sum(k["total_ms_per_solve"] for k in kernels.values()) / ms_per_step, 2)},
+        # with streams > 1: the dominant class's algorithmic bytes per solve over its share of the solve's wall time
+        # (its share of the summed event time) -- an estimate of the rate the concurrent launches reach together
+        "concurrent_estimate": None if nstreams <= 1 else {
+            "achieved_GBps": round(kernels[dom]["algorithmic_bytes_per_launch"] * kernels[dom]["launches_per_solve"]
+                                   / (ms_per_step * 1e-3 * kernels[dom]["total_ms_per_solve"]
+                                      / sum(k["total_ms_per_solve"] for k in kernels.values())) / 1e9, 1)},
+        "whole_solve": {
+            # the bytes of the path that ran (fused: plane_bytes_per_px; 2-pass: SURVEY s8d canonical)
+            "algorithmic_bytes": alg_bytes,
+            "achieved_GBps": round(alg_bytes / (ms_per_step * 1e-3) / 1e9, 1),
+            "frac": round(alg_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+            # SURVEY.md s8d's byte model of the 2-pass form (the spectrum round-trips through HBM twice per
+            # iteration): what a 2-pass solve would have to move, NOT bytes this run moved
+            "survey_2pass_model_bytes": canonical_bytes(M, N, K) * planes,
+        },
+    }
+    return kernels, roofline
 
 
 def main():
@@ -508,9 +622,16 @@ def main():
     value = images / el
     ms_per_step = 1000.0 * el / max(args.steps, 1)
 
+    if args.dump_outputs:
+        # what the last timed step handed its caller: the solved batch; N > 1: rank 0's gathered batch (a
+        # collective call), or with --no-gather rank 0's own shard
+        x = sg.gathered() if sg is not None else out
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"x": x})
+
     ranks = None
     solve_only = None
-    if world > 1:
+    if world > 1 and args.full:
         # diagnostics for the multi-GPU record (outside the timed region above): the same steps solve-only (no
         # gather) in this invocation, and per rank what it saw -- which engine ran, how long its own steps took,
         # how long its gathers ran past its last solve, and which device it drove
@@ -551,66 +672,11 @@ def main():
                                           "value": alt["value"],
                                           "note": "same steps gathered by the other engine, max over ranks (not the metric)"}
 
-    # ---- per-kernel timing (separate instrumented solve; not part of the timed region) ----
-    _lib.profile_reset()
-    _lib.profile_enable(True)
-    reps = 2
-    for _ in range(reps):
-        admm_deconv.tvd_fft(y, synth.LAMBDA, synth.RHO, h, False, K, out=out, workspace=ws[0], stream=stream)
-    _lib.profile_enable(False)
-    planes = B * P
-    # planes per launch: the MALL-resident schedule runs large 2-pass batches as chunks on several streams
-    chunk, nstreams = _lib.forward_schedule(M, N, False, cfg["psf"][0], planes)
-    kb = kernel_bytes_per_plane(M, N, K)
-    kernels = {}
-    for cls, name in _lib.KERNEL_CLASSES.items():
-        ms, n = _lib.profile_get(cls)
-        if n == 0:
-            continue
-        avg_ms = ms / n
-        e = {"launches_per_solve": n // reps, "avg_ms": avg_ms, "total_ms_per_solve": ms / reps}
-        if name in kb:
-            e["algorithmic_bytes_per_launch"] = kb[name] * chunk
-            e["achieved_GBps"] = kb[name] * chunk / (avg_ms * 1e-3) / 1e9
-        kernels[name] = e
-    dom = max((k for k in kernels if k in kb), key=lambda k: kernels[k]["total_ms_per_solve"])
-    alg_bytes = kb["plane"] * planes if "plane" in kernels else canonical_bytes(M, N, K) * planes
-    traffic = load_traffic(config, dom, planes=chunk)
-    ach = kernels[dom]["achieved_GBps"]
-    roofline = {
-        "bound": "hbm", "kernel": dom, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-        "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic,
-        # against the measured streaming ceiling of the same read/write mix (not the 8 TB/s spec)
-        "achievable_peak": achievable_gbs(),
-        "frac_of_achievable": round(ach / achievable_gbs(), 4) if achievable_gbs() else None,
-        "algorithmic_bytes_per_launch": kernels[dom]["algorithmic_bytes_per_launch"],
-        "avg_launch_ms": round(kernels[dom]["avg_ms"], 5),
-        "compute": compute_side(config, dom, kernels[dom]["avg_ms"], chunk),
-        # launches of `chunk_planes` planes; with streams > 1 that many chunks' launches run concurrently, so a
-        # launch's duration includes its share of the chip (the whole-solve figure below is the aggregate)
-        # (rocprofv3's begin -> end of the same launches is shorter: profiles/r06_c4_mall_kernel_stats.csv, DESIGN.md
-        # s5); overlap = the kernels' event time per solve over the solve's wall time
-        "schedule": {"chunk_planes": chunk, "streams": nstreams,
-                     "overlap": round(sum(k["total_ms_per_solve"] for k in kernels.values()) / ms_per_step, 2)},
-        # with streams > 1: the dominant class's algorithmic bytes per solve over its share of the solve's wall time
-        # (its share of the summed event time) -- an estimate of the rate the concurrent launches reach together
-        "concurrent_estimate": None if nstreams <= 1 else {
-            "achieved_GBps": round(kernels[dom]["algorithmic_bytes_per_launch"] * kernels[dom]["launches_per_solve"]
-                                   / (ms_per_step * 1e-3 * kernels[dom]["total_ms_per_solve"]
-                                      / sum(k["total_ms_per_solve"] for k in kernels.values())) / 1e9, 1)},
-        "whole_solve": {
-            # the bytes of the path that ran (fused: plane_bytes_per_px; 2-pass: SURVEY s8d canonical)
-            "algorithmic_bytes": alg_bytes,
-            "achieved_GBps": round(alg_bytes / (ms_per_step * 1e-3) / 1e9, 1),
-            "frac": round(alg_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-            # SURVEY.md s8d's byte model of the 2-pass form (the spectrum round-trips through HBM twice per
-            # iteration): what a 2-pass solve would have to move, NOT bytes this run moved
-            "survey_2pass_model_bytes": canonical_bytes(M, N, K) * planes,
-        },
-    }
-
+    kernels, roofline = None, None
+    if args.full:
+        kernels, roofline = kernels_roofline(config, cfg, B, y, h, out, ws[0], stream, ms_per_step)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, psf_np, base, args.cpu_seconds)
 
     if rank == 0:
@@ -628,10 +694,9 @@ def main():
                            (" + IPC push gather (async peer copies over xGMI)" if sg.engine == "ipc" else
                             " + RCCL gather" if args.backend == "nccl" else " + gloo gather") + " (overlapped, "
                            f"{args.chunks} chunk{'s' if args.chunks > 1 else ''}/shard)" if gather else "")},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "kernels": kernels,
         }
+        if args.full:
+            line.update(roofline=roofline, cpu_baseline=cpu, kernels=kernels)
         if ranks is not None:
             line["ranks"] = ranks
             line["solve_only"] = solve_only

@@ -4,7 +4,8 @@ The reference ships no golden vectors; these fixtures pin the ora
 fp32 inputs produced by admm_deconv.synth (seeded, counter-based), so the GPU tests can compare
 against committed data as well as against a live oracle run.  Each fixture stores the float32 input
 y (C layout (B,P,N,M)), the PSF h (C layout (kw,kh), possibly empty), the solver parameters and the
-fp64 oracle output rounded to float32.
+fp64 oracle output rounded to float32.  No committed file may exceed 1 MiB: where y and x together would, y goes
+to tests/golden/inputs/ under the same file name (tests/golden_fixtures.py reads both).
 
     python tests/golden/gen_golden.py          # rewrites tests/golden/*.npz and manifest.json
 """
@@ -33,6 +34,8 @@ FIXTURES = [
     ("c4_512_k50_plane", 1, 1, 512, 512, ("gauss", 15, 2.5), 0.0041, 0.021, False, 50),
 ]
 
+SPLIT_BYTES = 1 << 20   # y + x (uncompressed) above this: y in inputs/ (noise does not compress)
+
 
 def psf_of(spec, seed):
     if spec is None:
@@ -55,8 +58,11 @@ def main():
                                                      np.float32(rho), oracle_np.psf_from_c(h) if h.size else None,
                                                      iso, K))
         params = dict(lam=lam, rho=rho, iso=iso, K=K, B=B, P=P, N=N, M=M, psf=list(psf) if psf else None)
-        np.savez_compressed(os.path.join(HERE, name + ".npz"), y=y, h=h, x=x.astype(np.float32),
-                            params=np.array(json.dumps(params)))
+        arrays = dict(y=y, h=h, x=x.astype(np.float32), params=np.array(json.dumps(params)))
+        if y.nbytes + arrays["x"].nbytes > SPLIT_BYTES:
+            os.makedirs(os.path.join(HERE, "inputs"), exist_ok=True)
+            np.savez_compressed(os.path.join(HERE, "inputs", name + ".npz"), y=arrays.pop("y"))
+        np.savez_compressed(os.path.join(HERE, name + ".npz"), **arrays)
         manifest[name] = params
         print(name, y.shape, h.shape, float(np.abs(x).max()))
     json.dump(manifest, open(os.path.join(HERE, "manifest.json"), "w"), indent=1)

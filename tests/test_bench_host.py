@@ -37,3 +37,27 @@ def test_traffic_without_plane_count_is_the_profiled_entry(planes):
     b = _bench()
     assert b.load_traffic("c2", "plane", planes=planes) is not None
     assert b.load_traffic("no-such-config", "plane") is None
+
+
+def test_dump_outputs_small_tensors_whole_large_ones_sampled(tmp_path):
+    """--dump-outputs: tensors within the size limit are written whole as float32; of a larger one the same seeded
+    sample of planes in every run, and all files together stay below 64 MB."""
+    import numpy as np
+    import torch
+    b = _bench()
+    g = torch.Generator().manual_seed(1)
+    small = torch.rand(3, 2, 8, 8, generator=g)
+    big = torch.rand(b.DUMP_BYTES // (2 * 64 * 64 * 4) + 37, 64, 64, generator=g)   # past its half of the limit
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), {"small": small, "big": big, "half": small.half()})
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("small", "big", "half")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["small"], small.numpy()) and np.array_equal(got["half"], small.half().float().numpy())
+    share = b.DUMP_BYTES // 3
+    n = share // (64 * 64 * 4)
+    assert got["big"].shape == (n, 64, 64) and n < big.shape[0]
+    # the sample is planes of `big`, in ascending order, and the same in the second dump
+    idx = np.sort(np.random.default_rng(0).choice(big.shape[0], n, replace=False))
+    assert np.array_equal(got["big"], big.numpy()[idx])
+    assert np.array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < 64e6

@@ -136,10 +136,11 @@ def test_c3_full_size_eight_ranks(dev):
 
 def test_bench_two_ranks_gloo(dev):
     """bench.py --gpus 2 spawns its two ranks and runs the c3 schedule (here over gloo, both ranks on
-    this box's one GPU, with a small batch); rank 0 prints one JSON line with n_gpus 2."""
+    this box's one GPU, with a small batch); rank 0 prints one JSON line with n_gpus 2, with --full the per-rank
+    diagnostics and the solve-only / other-engine legs in it."""
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--backend", "gloo",
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--backend", "gloo", "--full",
                         "--batch", "8", "--steps", "2", "--warmup", "1", "--distinct", "4", "--chunks", "2"],
                        capture_output=True, text=True, timeout=300, env=env, cwd=repo)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import admm_deconv
+import golden_fixtures
 from parity import assert_parity
 
 pytestmark = pytest.mark.gpu
@@ -16,7 +17,7 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
 @pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLD, "*.npz"))), ids=os.path.basename)
 def test_gpu_matches_fixture(dev, path):
-    d = np.load(path)
+    d = golden_fixtures.load(path)
     p = json.loads(str(d["params"]))
     y = torch.from_numpy(d["y"]).to(dev)
     h = torch.from_numpy(d["h"]).to(dev) if d["h"].size else None

@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import golden_fixtures
 import oracle_c
 import oracle_np as o
 from parity import PROX_MIN_FRACTION
@@ -129,7 +130,7 @@ def test_prox_stats_separate_linear_from_live_cases():
 
 @pytest.mark.parametrize("path", sorted(glob.glob(os.path.join(GOLD, "*.npz"))), ids=os.path.basename)
 def test_golden_fixture_reproduces(path):
-    d = np.load(path)   # allow_pickle=False (default)
+    d = golden_fixtures.load(path)
     p = json.loads(str(d["params"]))
     h = d["h"] if d["h"].size else None
     st = {}

@@ -9,6 +9,6 @@ O=gpurun_out/${TAG}_configs.jsonl
 for a in "--config c1 --steps 50" "--steps 20" "--config c4 --steps 5 --warmup 2" "--config c5 --steps 5 --warmup 2" \
          "--config c5 --iso --steps 5 --warmup 2" "--config c5 --iso --batch 2 --steps 20" "--config c5 --batch 2 --steps 20"; do
   echo "== $a"
-  timeout -k 10 300 python bench.py --no-cpu-baseline $a >> $O 2>> gpurun_out/${TAG}_configs.err || { echo "rc=$? ($a)"; exit 1; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline $a >> $O 2>> ${O%.jsonl}.err || { echo "rc=$? ($a)"; exit 1; }
   tail -1 $O | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['unit'], d['ms_per_step'], (d.get('roofline') or {}).get('frac'))"
 done

@@ -11,7 +11,7 @@ for iso in "--iso" ""; do
     for lt in ${LTS:-0 4 2}; do
         for ct in ${CTS:-0 512 1024}; do
             echo "== $iso LINE_T=$lt COL_THREADS=$ct"
-            timeout -k 10 120 python bench.py --config c5 $iso --batch 2 --steps 20 --warmup 3 \
+            timeout -k 10 120 python bench.py --full --config c5 $iso --batch 2 --steps 20 --warmup 3 \
                 --opt LINE_T=$lt --opt COL_THREADS=$ct > gpurun_out/${TAG}_one.json 2>> gpurun_out/${TAG}_sweep.err || exit $?
             python - "$iso" "$lt" "$ct" gpurun_out/${TAG}_one.json >> $O <<'EOF'
 import json, sys
