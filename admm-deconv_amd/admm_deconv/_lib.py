@@ -42,7 +42,8 @@ EXPORTS = ("admm_abi_version", "admm_last_error", "admm_tvd_workspace_bytes", "a
            "admm_profile_enable", "admm_profile_reset", "admm_profile_get",
            "admm_tvd_multi_workspace_bytes", "admm_tvd_forward_multi_dev_f32",
            "admm_tvd_backward_multi_recorded_dev_f32", "admm_copy_async", "admm_query_paths", "admm_query_forward_schedule", "admm_clamp_backward_f32",
-           "admm_path_name", "admm_ipc_get_handle", "admm_ipc_open", "admm_ipc_close")
+           "admm_path_name", "admm_ipc_get_handle", "admm_ipc_open", "admm_ipc_close",
+           "admm_tvd_grouped_workspace_bytes", "admm_tvd_forward_grouped_dev_f32", "admm_query_grouped_path")
 
 # record flags (the want_hbar word of the record entry points) and multi-branch flags
 REC_HBAR, REC_MASKS = 1, 2
@@ -168,6 +169,14 @@ def load():
     L.admm_query_forward_schedule.restype = c_int
     L.admm_query_forward_schedule.argtypes = [c_int] * 4 + [ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong),
                                               ctypes.POINTER(c_int)]
+    L.admm_tvd_grouped_workspace_bytes.restype = c_int
+    L.admm_tvd_grouped_workspace_bytes.argtypes = [c_int] * 9 + [ctypes.POINTER(c_size_t)]
+    L.admm_tvd_forward_grouped_dev_f32.restype = c_int
+    L.admm_tvd_forward_grouped_dev_f32.argtypes = [c_void_p, c_void_p] + [c_int] * 6 + [c_void_p, c_int, c_int, c_void_p,
+                                                                                      c_void_p, c_int, c_int, c_int,
+                                                                                      c_void_p, c_size_t, c_void_p]
+    L.admm_query_grouped_path.restype = c_int
+    L.admm_query_grouped_path.argtypes = [c_int] * 4 + [ctypes.c_longlong, c_int, ctypes.POINTER(c_int)]
     L.admm_path_name.restype = ctypes.c_char_p
     L.admm_path_name.argtypes = [c_int]
     _lib = L
@@ -199,6 +208,20 @@ def multi_workspace_bytes(M, N, P, B, nbranch, maxit, flags):
     out = ctypes.c_size_t(0)
     check(load().admm_tvd_multi_workspace_bytes(M, N, P, B, nbranch, int(maxit), int(flags), ctypes.byref(out)))
     return out.value
+
+
+def grouped_workspace_bytes(M, N, P, B, gb, gp, kh, kw, iso):
+    out = ctypes.c_size_t(0)
+    check(load().admm_tvd_grouped_workspace_bytes(M, N, P, B, gb, gp, kh, kw, int(bool(iso)), ctypes.byref(out)))
+    return out.value
+
+
+def query_grouped_path(M, N, iso=False, kh=0, planes=0, groups=1):
+    """admm_query_grouped_path: the forward path name of a grouped call of `planes` planes in `groups` groups."""
+    L = load()
+    f = ctypes.c_int(0)
+    check(L.admm_query_grouped_path(M, N, int(bool(iso)), kh, int(planes), int(groups), ctypes.byref(f)))
+    return L.admm_path_name(f.value).decode()
 
 
 MODE_FORWARD, MODE_RECORD, MODE_BACKWARD = 0, 1, 2

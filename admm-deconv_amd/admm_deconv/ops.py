@@ -20,7 +20,7 @@ import torch
 from . import _lib
 
 __all__ = ["tvd_fft", "tvd_fft_backward", "tvd_fft_record", "tvd_fft_backward_recorded", "Recording", "Workspace",
-           "tvd_fft_multi", "tvd_fft_multi_backward_recorded", "multi_supported"]
+           "tvd_fft_multi", "tvd_fft_multi_backward_recorded", "multi_supported", "tvd_fft_grouped"]
 
 
 class Workspace:
@@ -435,6 +435,92 @@ def tvd_fft(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, out=None, wo
 
 # ---- several ADMM branches of one shared input (Parallel(chcat, ...), src/nets/net_build.jl:113-125) ----
 MULTI_M = MULTI_N = 256
+
+
+def _group_params(v, name, G, device):
+    """lambda / rho of a grouped solve as a device float32 tensor of 1 or G elements (no host read)."""
+    if isinstance(v, torch.Tensor):
+        if v.numel() not in (1, G):
+            raise ValueError(f"tvd_fft_grouped: {name} must have 1 or {G} (= gb * gp) elements, got {v.numel()}")
+        t = v.detach().reshape(-1)
+        if t.device != device:
+            if t.device.type == "cuda":
+                raise ValueError(f"{name} is on {t.device}, the solve on {device}")
+            t = t.to(device)
+        return t.to(torch.float32).contiguous()
+    return torch.full((1,), _scalar(v, name), dtype=torch.float32, device=device)
+
+
+def tvd_fft_grouped(y, lam, rho, h, isotropic=False, maxit=100, *, out=None, workspace=None, stream=None):
+    """tvd_fft with a PSF, lambda and rho per image or per channel, in one call
+    (admm_tvd_forward_grouped_dev_f32, include/admm_deconv.h).
+
+    y:   float32 (B, P, N, M) on a ROCm device.
+    h:   (gb, gp, kw, kh) with gb in {1, B} and gp in {1, P} -- plane (b, p) is solved with the PSF
+         h[b if gb > 1 else 0, p if gp > 1 else 0] -- or None: no PSF; the groups then follow the parameter count
+         (B * P values: per plane, B: per image, P: per channel, 1: one group; with B == P, B values name neither and
+         are refused: give B * P).
+    lam, rho: floats, or tensors of 1 or gb * gp elements (group order b * gp + p); they stay on the device.
+    isotropic: the batch coupling of the reference is kept over ALL planes, so lam and rho must have one element.
+    Forward only: the grouped adjoint does not exist yet."""
+    if not isinstance(y, torch.Tensor) or y.device.type != "cuda" or y.dtype != torch.float32:
+        raise TypeError("tvd_fft_grouped: y must be a float32 torch tensor on a ROCm device")
+    if y.dim() != 4:
+        raise ValueError("tvd_fft_grouped: y must be 4-D (B, P, N, M)")
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (y, h, lam, rho)):
+        raise NotImplementedError("tvd_fft_grouped is forward only: the grouped adjoint does not exist yet "
+                                  "(detach the inputs, or loop tvd_fft per group under autograd)")
+    y4 = y.detach().contiguous()
+    B, P, N, M = y4.shape
+    if h is None:
+        gb = gp = 1
+        hbuf, hp, kh, kw = None, None, 0, 0
+        pg = [t.numel() for t in (lam, rho) if isinstance(t, torch.Tensor) and t.numel() > 1]
+        if pg:   # no PSF: the groups come from the parameter count (per plane, per image or per channel)
+            n = pg[0]
+            if n == B * P:
+                gb, gp = B, P
+            elif n == B and n == P:
+                raise ValueError(f"tvd_fft_grouped: {n} parameters without a PSF are ambiguous when B == P == {n} (per "
+                                 "image or per channel?): give B * P values, one per plane in (b, p) order")
+            elif n == B:
+                gb = B
+            elif n == P:
+                gp = P
+            else:
+                raise ValueError(f"tvd_fft_grouped: {n} parameters fit neither B = {B}, P = {P} nor B * P planes")
+    else:
+        if not isinstance(h, torch.Tensor) or h.dim() != 4:
+            raise ValueError("tvd_fft_grouped: h must be a 4-D tensor (gb, gp, kw, kh) or None")
+        gb, gp, kw, kh = h.shape
+        if gb not in (1, B) or gp not in (1, P):
+            raise ValueError(f"tvd_fft_grouped: h's leading dims ({gb}, {gp}) must be (1 or B = {B}, 1 or P = {P})")
+        hbuf = h.detach().to(device=y.device, dtype=torch.float32).contiguous()
+        hp = hbuf.data_ptr()
+    G = gb * gp
+    lt, rt = _group_params(lam, "lambda", G, y.device), _group_params(rho, "rho", G, y.device)
+    nparam = max(lt.numel(), rt.numel())
+    if lt.numel() != nparam:
+        lt = lt.expand(nparam).contiguous()
+    if rt.numel() != nparam:
+        rt = rt.expand(nparam).contiguous()
+    if out is None:
+        out = torch.empty_like(y4)
+    elif out.shape != y4.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != y.device:
+        raise ValueError("out must be a contiguous float32 tensor of y's shape on y's device")
+    stream, s_handle = _stream_of(stream, y.device)
+    nbytes = _lib.grouped_workspace_bytes(M, N, P, B, gb, gp, kh, kw, isotropic)
+    if workspace is None:
+        workspace = _default_workspace("grouped", y.device, stream)
+    ws_ptr, ws_len = workspace.get(nbytes, y.device, stream)
+    if isinstance(stream, torch.cuda.Stream) and stream != torch.cuda.current_stream(y.device):
+        for t in (lt, rt, hbuf):
+            if t is not None:
+                t.record_stream(stream)
+    _lib.check(_lib.load().admm_tvd_forward_grouped_dev_f32(
+        y4.data_ptr(), out.data_ptr(), M, N, P, B, gb, gp, hp, kh, kw, lt.data_ptr(), rt.data_ptr(), nparam,
+        int(bool(isotropic)), int(maxit), ws_ptr, ws_len, s_handle))
+    return out
 
 
 def multi_supported(y, isotropic=False, psf=None, group=None):

@@ -313,6 +313,65 @@ int forward_impl(const float* y, float* x_out, int M, int N, int P, int B, const
     return rc;
 }
 
+GroupedLayout make_grouped_layout(int M, int N, size_t planes, int groups, bool psf, bool iso) {
+    GroupedLayout L{};
+    L.f = make_layout(M, N, planes, psf, iso);
+    size_t off = align_up(L.f.total);
+    auto take = [&](size_t bytes) {
+        size_t o = off;
+        off = align_up(off + bytes);
+        return o;
+    };
+    const size_t G = (size_t)groups;
+    L.tab_f = (unsigned)(align_up((size_t)(M / 2 + 1) * N * 4) / 4);
+    L.f.prm = take(G * 16);
+    L.f.C = take(G * L.tab_f * 4);
+    L.f.G = psf ? take(G * L.tab_f * 8) : 0;
+    L.f.F = fused_tables_shape(M, N) ? take(G * admm::plane::grouped_tables_bytes()) : 0;
+    L.total = L.f.total = off;
+    return L;
+}
+
+// validation shared by the grouped workspace query and the grouped call
+int check_grouped(int M, int N, int P, int B, int gb, int gp, int kh, int kw, int iso) {
+    int rc = check_shape(M, N, P, B, kh, kw, iso);
+    if (rc) return rc;
+    if ((gb != 1 && gb != B) || (gp != 1 && gp != P))
+        return fail(ADMM_E_INVALID, "grouped solve: gb must be 1 or B, gp 1 or P (gb=%d gp=%d B=%d P=%d)", gb, gp, B, P);
+    if ((size_t)P * B > kChunkPlanes)
+        return fail(ADMM_E_UNSUPPORTED, "grouped solve: at most %zu planes per call", kChunkPlanes);
+    return ADMM_OK;
+}
+
+int forward_grouped(const float* y, float* x_out, int M, int N, int P, int B, int gb, int gp, const float* h, int kh,
+                    int kw, const float* lambda, const float* rho, int nparam, int iso, int maxit, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    int rc = check_grouped(M, N, P, B, gb, gp, kh, kw, iso);
+    if (rc) return rc;
+    const int G = gb * gp;
+    if (kh > 0 && !h) return fail(ADMM_E_INVALID, "grouped solve: h is NULL with a %d x %d PSF", kh, kw);
+    if (!lambda || !rho) return fail(ADMM_E_INVALID, "grouped solve: lambda and rho must be device pointers");
+    if (nparam != 1 && nparam != G)
+        return fail(ADMM_E_INVALID, "grouped solve: nparam must be 1 or the group count %d (got %d)", G, nparam);
+    if (iso && nparam > 1)
+        return fail(ADMM_E_UNSUPPORTED, "grouped solve: the isotropic prox is one BT factor map per batch, so it takes "
+                                        "one (lambda, rho) pair (nparam = 1), got %d", nparam);
+    rc = check_common(y, x_out, maxit);
+    if (rc) return rc;
+    const size_t planes = (size_t)P * B;
+    const GroupedLayout L = make_grouped_layout(M, N, planes, G, kh > 0, iso != 0);
+    rc = check_ws(workspace, workspace_bytes, L.total);
+    if (rc) return rc;
+    rec_forget(workspace);
+    const int path = plan_grouped(M, N, iso != 0, planes);
+    const admm::plane::Branches br = admm::plane::grouped_branches(P, B, gb, gp, L.tab_f, nparam > 1 ? 4u : 0u);
+    Launcher ln{reinterpret_cast<hipStream_t>(stream), g_prof.on, {}};
+    rc = run_forward(ln, y, x_out, M, N, planes, h, kh, kw, admm::ScalarSrc{lambda, rho, 0.f, 0.f}, iso, maxit,
+                     static_cast<unsigned char*>(workspace), L.f, Traj{}, nullptr, path, true, &br);
+    const int rc2 = ln.finish();
+    return rc ? rc : rc2;
+}
+
 // phases: 1 = forward recording the trajectory into the workspace (writes x_out), 2 = reverse sweep
 // from a recorded workspace (x_out = that forward's output), 3 = both.  rec_flags (ADMM_REC_*): phase 1 alone
 // records the extra h_bar trajectory only when asked (phase 2 must then be given h_bar).
@@ -741,6 +800,22 @@ int admm_ipc_close(void* dev_ptr, int device) {
     if (prev != device) (void)hipSetDevice(prev);
     if (e != hipSuccess) return fail(ADMM_E_HIP, "admm_ipc_close: %s", hipGetErrorString(e));
     return ADMM_OK;
+}
+
+int admm_tvd_grouped_workspace_bytes(int M, int N, int P, int B, int gb, int gp, int kh, int kw, int iso,
+                                     size_t* out_bytes) {
+    if (!out_bytes) return fail(ADMM_E_INVALID, "out_bytes is NULL");
+    const int rc = check_grouped(M, N, P, B, gb, gp, kh, kw, iso);
+    if (rc) return rc;
+    *out_bytes = make_grouped_layout(M, N, (size_t)P * B, gb * gp, kh > 0, iso != 0).total;
+    return ADMM_OK;
+}
+
+int admm_tvd_forward_grouped_dev_f32(const float* y, float* x_out, int M, int N, int P, int B, int gb, int gp,
+                                     const float* h, int kh, int kw, const float* lambda, const float* rho, int nparam,
+                                     int iso, int maxit, void* workspace, size_t workspace_bytes, void* stream) {
+    return forward_grouped(y, x_out, M, N, P, B, gb, gp, h, kh, kw, lambda, rho, nparam, iso, maxit, workspace,
+                           workspace_bytes, stream);
 }
 
 int admm_tvd_multi_workspace_bytes(int M, int N, int P, int B, int nbranch, int maxit, int flags, size_t* out_bytes) {

@@ -328,13 +328,19 @@ __global__ __launch_bounds__(256) void column_kernel(const float2* __restrict__ 
                                                      const float* __restrict__ Ct, const float2* __restrict__ Gt,
                                                      const float2* __restrict__ twN, FPlan pN, int H, int KB,
                                                      int mode, float cs, float2* __restrict__ vsave = nullptr,
-                                                     double* __restrict__ Qp = nullptr, float2* __restrict__ yh = nullptr) {
+                                                     double* __restrict__ Qp = nullptr, float2* __restrict__ yh = nullptr,
+                                                     Branches br = kOneSolve) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int N = pN.n;
     float2* A = reinterpret_cast<float2*>(smem_raw);
     float2* B = A + (size_t)KB * N;
     const XBlk xb = xcd_block();   // XCD-aware block order (admm_kernels.hip): neighbours share L2 lines
     const int plane = xb.y, k0 = xb.x * KB;
+    {   // a grouped solve: the plane's group tables, tab_f floats (Ct) / float2 (Gt) apart
+        const size_t tab = br.nbr == 0 ? (size_t)plane::group_of(br, plane) * br.tab_f : 0;
+        Ct += tab;
+        if (Gt) Gt += tab;
+    }
     const int kc = min(KB, H - k0);
     const float2* sp = src + (size_t)plane * N * H + k0;
     float2* dp = dst + (size_t)plane * N * H + k0;
@@ -381,8 +387,8 @@ __global__ __launch_bounds__(256) void column_kernel(const float2* __restrict__ 
 __global__ __launch_bounds__(256) void line_upd_kernel(const float* __restrict__ x, const float* __restrict__ s_old,
                                                        float* __restrict__ s_new, const float* __restrict__ hty,
                                                        float2* __restrict__ spec, const float2* __restrict__ twM,
-                                                       FPlan pM, int N, int Tg, const float* __restrict__ prm, int first) {
-    const float tau = prm[0]; const float rho = prm[1];   // device-resident scalars (setup_kernel)
+                                                       FPlan pM, int N, int Tg, const float* __restrict__ prm, int first,
+                                                       Branches br = kOneSolve) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int M = pM.n, H = M / 2 + 1;
     const size_t MN = (size_t)M * N;
@@ -392,6 +398,8 @@ __global__ __launch_bounds__(256) void line_upd_kernel(const float* __restrict__
     float* W1 = W0 + (size_t)(Tg + 1) * M;                       // Tg lines
     const XBlk xb = xcd_block();   // XCD-aware block order (admm_kernels.hip): neighbours share L2 lines
     const int plane = xb.y, j0 = xb.x * Tg;
+    if (br.nbr == 0) prm += (size_t)plane::group_of(br, plane) * br.prm_f;   // a grouped solve: the plane's group scalars
+    const float tau = prm[0]; const float rho = prm[1];   // device-resident scalars (setup_kernel)
     const int T = min(Tg, N - j0);   // the last block of a plane may be ragged (gen_nb)
     const float* xp = x + (size_t)plane * MN;
     const float* so = s_old + (size_t)plane * 2 * MN;

@@ -90,11 +90,12 @@ __device__ __forceinline__ void write_prm(const ScalarSrc& sc, float* prm) {
     prm[1] = rho;
     prm[2] = lam;
 }
-__global__ __launch_bounds__(kThreads) void setup_kernel(float2* __restrict__ twM, float2* __restrict__ twN,
-                                                         float* __restrict__ Ct, float2* __restrict__ Gt,
-                                                         const float* __restrict__ h, int kh, int kw, int M,
-                                                         int N, ScalarSrc sc, float* __restrict__ prm,
-                                                         double2* __restrict__ SigT) {
+// tw_out: this block row also stores the twiddle tables (setup_grouped_kernel: group 0 only)
+__device__ __forceinline__ void setup_body(float2* __restrict__ twM, float2* __restrict__ twN,
+                                           float* __restrict__ Ct, float2* __restrict__ Gt,
+                                           const float* __restrict__ h, int kh, int kw, int M, int N,
+                                           const ScalarSrc& sc, float* __restrict__ prm,
+                                           double2* __restrict__ SigT, bool tw_out) {
     const float rho = src_rho(sc);
     if (blockIdx.x == 0 && threadIdx.x == 0) write_prm(sc, prm);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -118,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void setup_kernel(float2* __restrict__ tw
         for (int t = threadIdx.x; t < kh * kw; t += blockDim.x) hl[t] = h[t];
     const float* hs = psf_lds ? hl : h;
     __syncthreads();
-    if (blockIdx.x == 0) {
+    if (blockIdx.x == 0 && tw_out) {
         for (int t = threadIdx.x; t < M; t += blockDim.x) twM[t] = make_float2((float)tM[t].x, (float)tM[t].y);
         for (int t = threadIdx.x; t < N; t += blockDim.x) twN[t] = make_float2((float)tN[t].x, (float)tN[t].y);
     }
@@ -182,6 +183,30 @@ __global__ __launch_bounds__(kThreads) void setup_kernel(float2* __restrict__ tw
         const double lap = 4.0 * sx * sx + 4.0 * sy * sy;   // |Lx|^2 + |Ly|^2 (ops.jl:35-36)
         Ct[q] = (float)(inv_mn / (s2 + (double)rho * lap));
     }
+}
+__global__ __launch_bounds__(kThreads) void setup_kernel(float2* __restrict__ twM, float2* __restrict__ twN,
+                                                         float* __restrict__ Ct, float2* __restrict__ Gt,
+                                                         const float* __restrict__ h, int kh, int kw, int M,
+                                                         int N, ScalarSrc sc, float* __restrict__ prm,
+                                                         double2* __restrict__ SigT) {
+    setup_body(twM, twN, Ct, Gt, h, kh, kw, M, N, sc, prm, SigT, true);
+}
+// Grouped solve: block row g = blockIdx.y builds group g's tables (Ct / Gt blocks tab_f floats / float2 apart, the
+// {tau, rho, lambda} blocks prm_f floats apart) from its own PSF h + g kh kw and its own lambda[g], rho[g] --
+// or, with one pair for all groups (nparam = 1, prm_f = 0), from lambda[0], rho[0]; every row then writes the
+// same scalar block.  The same arithmetic per bin as setup_kernel.
+__global__ __launch_bounds__(kThreads) void setup_grouped_kernel(float2* __restrict__ twM, float2* __restrict__ twN,
+                                                                 float* __restrict__ Ct, float2* __restrict__ Gt,
+                                                                 const float* __restrict__ h, int kh, int kw, int M,
+                                                                 int N, const float* __restrict__ lam,
+                                                                 const float* __restrict__ rho, int nparam,
+                                                                 float* __restrict__ prm, unsigned tab_f,
+                                                                 unsigned prm_f) {
+    const size_t g = blockIdx.y;
+    const size_t gs = nparam > 1 ? g : 0;
+    const ScalarSrc sc{lam + gs, rho + gs, 0.f, 0.f};
+    setup_body(twM, twN, Ct + g * tab_f, Gt ? Gt + g * tab_f : nullptr, h ? h + g * (size_t)kh * kw : nullptr, kh, kw, M,
+               N, sc, prm + g * prm_f, nullptr, g == 0);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -519,21 +544,28 @@ __device__ __forceinline__ void column_body(XBlk xb, const float2* src, float2* 
     }
 }
 
-template <int NN, int MUL, bool SAVE, bool ACCQ, int NT = kThreads, int YH = YH_NONE>
+// GRP: a grouped solve (br.nbr = 0): the plane's group C table, and its G table the same count of float2 apart
+template <int NN, int MUL, bool SAVE, bool ACCQ, int NT = kThreads, int YH = YH_NONE, bool GRP = false>
 __global__ __launch_bounds__(NT) void column_kernel(const float2* src, float2* dst, const float* __restrict__ Ct,
                                                     const float2* __restrict__ Gt, const float2* __restrict__ twN, int L,
                                                     int KB, float cs, float2* __restrict__ vsave,
                                                     double* __restrict__ Qp, Branches br = kOneSolve,
                                                     float2* __restrict__ yh = nullptr) {
     const XBlk xb = xcd_block();
+    if constexpr (GRP) {
+        const size_t tab = (size_t)plane::group_of(br, xb.y) * br.tab_f;
+        column_body<NN, MUL, SAVE, ACCQ, NT, YH>(xb, src, dst, Ct + tab, Gt ? Gt + tab : nullptr, twN, L, KB, cs, vsave,
+                                                 Qp, yh);
+    } else {
     column_body<NN, MUL, SAVE, ACCQ, NT, YH>(xb, src, dst, Ct + (size_t)branch_of(br, xb.y).i * br.tab_f, Gt, twN, L,
                                              KB, cs, vsave, Qp, yh);
+    }
 }
 
 // ----------------------------------------------------------------------------------------------
 // LINE pass (iterations 1..K-1): T output lines + 1 halo line on each side.
 // ----------------------------------------------------------------------------------------------
-template <int L, int T, int NT = kThreads>
+template <int L, int T, int NT = kThreads, bool GRP = false>
 __device__ __forceinline__ void line_body(XBlk xb, const float2* __restrict__ spec1, float2* __restrict__ spec0,
                                           const float* __restrict__ s_old, float* __restrict__ s_new,
                                           const float* __restrict__ hty, const float2* __restrict__ twM, int N,
@@ -558,7 +590,8 @@ __device__ __forceinline__ void line_body(XBlk xb, const float2* __restrict__ sp
     const int tid = threadIdx.x;
     const float* so = s_old + (size_t)plane * 2 * MN;
     float* sn = s_new + (size_t)plane * 2 * MN;
-    const BranchOf bo = branch_of(br, plane);   // several branches: H^T y = the shared input plane, own scalars
+    // several branches: H^T y = the shared input plane, own scalars; GRP (a grouped solve): the plane's group scalars
+    const BranchOf bo = plane::plane_of<GRP>(br, plane);
     // hty NULL: H^T y is added in the spectral domain by the column pass (YH_ADD); v = rho D^T w here
     const float* hp = hty ? hty + bo.in_plane * MN : nullptr;
     const float tau = prm[(size_t)bo.i * br.prm_f], rho = prm[(size_t)bo.i * br.prm_f + 1];   // (setup_kernel)
@@ -721,12 +754,12 @@ __device__ __forceinline__ void line_body(XBlk xb, const float2* __restrict__ sp
     pack_store<L>(Z, spec0 + (size_t)plane * N * L, j0, T, N, tw);
 }
 
-template <int L, int T, int NT = kThreads>
+template <int L, int T, int NT = kThreads, bool GRP = false>
 __global__ __launch_bounds__(NT) void line_kernel(const float2* __restrict__ spec1, float2* __restrict__ spec0,
                                                   const float* __restrict__ s_old, float* __restrict__ s_new,
                                                   const float* __restrict__ hty, const float2* __restrict__ twM, int N,
                                                   const float* __restrict__ prm, int s_zero, Branches br = kOneSolve) {
-    line_body<L, T, NT>(xcd_block(), spec1, spec0, s_old, s_new, hty, twM, N, prm, s_zero, br);
+    line_body<L, T, NT, GRP>(xcd_block(), spec1, spec0, s_old, s_new, hty, twM, N, prm, s_zero, br);
 }
 
 // ----------------------------------------------------------------------------------------------

@@ -70,6 +70,20 @@ int launch_line_inv(int L, int T, dim3 g, size_t lds, hipStream_t s, const float
 int launch_line(int L, int T, dim3 g, size_t lds, hipStream_t s, const float2* spec1, float2* spec0,
                 const float* so, float* sn, const float* hty, const float2* twM, int N, const float* prm,
                 int sz, int nt = kThreads, const Branches& br = kOneSolve) {
+    if (br.nbr == 0) {   // a grouped solve: the GRP instantiations (group scalars per plane)
+#define X3(l, t, n)                                                                                       \
+        if (L == l && T == t && nt == n) {                                                                \
+            set_lds(line_kernel<l, t, n, true>, lds);                                                     \
+            line_kernel<l, t, n, true><<<g, n, lds, s>>>(spec1, spec0, so, sn, hty, twM, N, prm, sz, br); \
+            return 0;                                                                                     \
+        }
+#define X(l, t) X3(l, t, kThreads)
+        X3(256, 8, 512) X3(256, 16, 1024) X3(256, 4, 512) X3(256, 8, 1024)
+        ADMM_LT_CASES(X)
+#undef X
+#undef X3
+        return -1;
+    }
     if (nt != kThreads) {   // wider blocks at 512-point lines (update kernel, line_T_upd)
 #define X(l, t, n)                                                                                       \
         if (L == l && T == t && nt == n) {                                                               \
@@ -120,15 +134,15 @@ int launch_iso_b(int L, int T, dim3 g, size_t lds, hipStream_t s, const float* s
     return -1;
 }
 
-template <int MUL, bool SAVE, bool ACCQ, int YH = YH_NONE>
+template <int MUL, bool SAVE, bool ACCQ, int YH = YH_NONE, bool GRP = false>
 int launch_column_t(int N, dim3 g, size_t lds, hipStream_t s, const float2* src, float2* dst, const float* C,
                     const float2* G, const float2* twN, int L, int KB, float cs, float2* vsave, double* Qp,
                     const Branches& br, float2* yh = nullptr) {
     const int nt = column_threads(N);
 #define X(v)                                                                                                   \
     if (N == v && nt == kThreads) {                                                                            \
-        set_lds(column_kernel<v, MUL, SAVE, ACCQ, kThreads, YH>, lds);                                         \
-        column_kernel<v, MUL, SAVE, ACCQ, kThreads, YH><<<g, kThreads, lds, s>>>(src, dst, C, G, twN, L, KB, cs,  \
+        set_lds(column_kernel<v, MUL, SAVE, ACCQ, kThreads, YH, GRP>, lds);                                         \
+        column_kernel<v, MUL, SAVE, ACCQ, kThreads, YH, GRP><<<g, kThreads, lds, s>>>(src, dst, C, G, twN, L, KB, cs,  \
                                                                                   vsave, Qp, br, yh);             \
         return 0;                                                                                              \
     }
@@ -136,8 +150,8 @@ int launch_column_t(int N, dim3 g, size_t lds, hipStream_t s, const float2* src,
 #undef X
 #define X(v)                                                                                                   \
     if (N == v && nt == 512) {                                                                                 \
-        set_lds(column_kernel<v, MUL, SAVE, ACCQ, 512, YH>, lds);                                              \
-        column_kernel<v, MUL, SAVE, ACCQ, 512, YH><<<g, 512, lds, s>>>(src, dst, C, G, twN, L, KB, cs, vsave, Qp, br, \
+        set_lds(column_kernel<v, MUL, SAVE, ACCQ, 512, YH, GRP>, lds);                                              \
+        column_kernel<v, MUL, SAVE, ACCQ, 512, YH, GRP><<<g, 512, lds, s>>>(src, dst, C, G, twN, L, KB, cs, vsave, Qp, br, \
                                                                        yh);                                        \
         return 0;                                                                                              \
     }
@@ -145,8 +159,8 @@ int launch_column_t(int N, dim3 g, size_t lds, hipStream_t s, const float2* src,
 #undef X
 #define X(v)                                                                                                   \
     if (N == v && nt == 1024) {                                                                                \
-        set_lds(column_kernel<v, MUL, SAVE, ACCQ, 1024, YH>, lds);                                             \
-        column_kernel<v, MUL, SAVE, ACCQ, 1024, YH><<<g, 1024, lds, s>>>(src, dst, C, G, twN, L, KB, cs, vsave, Qp,  \
+        set_lds(column_kernel<v, MUL, SAVE, ACCQ, 1024, YH, GRP>, lds);                                             \
+        column_kernel<v, MUL, SAVE, ACCQ, 1024, YH, GRP><<<g, 1024, lds, s>>>(src, dst, C, G, twN, L, KB, cs, vsave, Qp,  \
                                                                          br, yh);                                   \
         return 0;                                                                                              \
     }
@@ -162,6 +176,11 @@ int launch_column_t(int N, dim3 g, size_t lds, hipStream_t s, const float2* src,
 int launch_column(int N, int mode, dim3 g, size_t lds, hipStream_t s, const float2* src, float2* dst,
                   const float* C, const float2* G, const float2* twN, int L, int KB, float cs,
                   float2* vsave = nullptr, double* Qp = nullptr, const Branches& br = kOneSolve, float2* yh = nullptr) {
+    if (br.nbr == 0) {   // a grouped solve (forward only: Y_h prep and the x-update)
+        if (mode == 5) return launch_column_t<1, false, false, YH_STORE, true>(N, g, lds, s, src, dst, C, G, twN, L, KB, cs, vsave, Qp, br, yh);
+        if (mode == 6) return launch_column_t<0, false, false, YH_ADD, true>(N, g, lds, s, src, dst, C, G, twN, L, KB, cs, vsave, Qp, br, yh);
+        return -1;
+    }
     switch (mode) {
         case 5: return launch_column_t<1, false, false, YH_STORE>(N, g, lds, s, src, dst, C, G, twN, L, KB, cs, vsave, Qp, br, yh);
         case 6: return launch_column_t<0, false, false, YH_ADD>(N, g, lds, s, src, dst, C, G, twN, L, KB, cs, vsave, Qp, br, yh);
@@ -194,7 +213,7 @@ admm::gen::FPlan make_fplan(int n) {
 
 int run_forward_generic(Launcher& ln, const float* y, float* x_out, int M, int N, size_t planes, int kh,
                         int iso, int maxit, unsigned char* ws, const Layout& lay,
-                        const Traj& tr, const admm_batch_reducer* red, int path);
+                        const Traj& tr, const admm_batch_reducer* red, int path, const Branches& br = kOneSolve);
 
 // the caller's cross-shard sum of an M x N map (isotropic prox over a sharded batch)
 int call_reducer(const admm_batch_reducer* red, float* buf, size_t count, hipStream_t s) {
@@ -246,7 +265,7 @@ int run_resident_iso(Launcher& ln, int M, int N, size_t planes, const float* hty
 
 int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t planes, const float* h, int kh,
                 int kw, const admm::ScalarSrc& sc, int iso, int maxit, unsigned char* ws, const Layout& lay,
-                const Traj& tr, const admm_batch_reducer* red, int fwd_path, bool tables) {
+                const Traj& tr, const admm_batch_reducer* red, int fwd_path, bool tables, const Branches* grp) {
     hipStream_t s = ln.s;
     int rc = ADMM_OK;
     const size_t MN = (size_t)M * N;
@@ -262,10 +281,23 @@ int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t
     float* prm = reinterpret_cast<float*>(ws + lay.prm);   // tau = lambda / rho (ops.jl:20), rho, lambda
     double2* SigT = tr.sig;
 
+    // a grouped solve: the 2-pass / runtime-length kernels' descriptor (C / G tables tab_f apart)
+    const Branches br = grp ? *grp : kOneSolve;
     if (tables) rc = ln.run(ADMM_K_SETUP, [&] {
         const size_t lds = (size_t)(M + N) * 16 + (kh * kw <= admm::kSetupPsfLds ? (size_t)kh * kw * 4 : 0);
         const int nb = (int)(((size_t)(L + 1) * N * (kh > 0 ? admm::kSetupSplit : 1) + kThreads - 1) / kThreads);
         const int grid = nb < 1024 ? (nb < 1 ? 1 : nb) : 1024;
+        if (grp) {   // every group's tables and scalars in one launch (block row = group)
+            const int G = admm::plane::grouped_count(br);
+            // every block computes the M + N fp64 twiddles before its bins: with many groups, fewer blocks per group
+            // (down to an eighth, while 2048 blocks remain) walk more bins each -- the same arithmetic per bin
+            int gx = grid;
+            while (gx > 1 && gx > grid / 8 && (size_t)G * (gx / 2) >= 2048) gx /= 2;
+            set_lds(admm::setup_grouped_kernel, lds);
+            hipLaunchKernelGGL(admm::setup_grouped_kernel, dim3(gx, (unsigned)G), dim3(kThreads), lds, s, twM, twN, Ct,
+                               Gt, h, kh, kw, M, N, sc.lam, sc.rho, br.prm_f ? G : 1, prm, br.tab_f, br.prm_f);
+            return;
+        }
         set_lds(admm::setup_kernel, lds);
         hipLaunchKernelGGL(admm::setup_kernel, dim3(grid), dim3(kThreads), lds, s, twM, twN, Ct, Gt, h, kh, kw, M,
                            N, sc, prm, SigT);
@@ -279,18 +311,24 @@ int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t
 
     const int path = fwd_path;
     if (generic_shape(M, N)) {   // ADMM_PATH_RESIDENT (smooth sides), _SMOOTH, _RUNTIME: the runtime-length layout
-        return run_forward_generic(ln, y, x_out, M, N, planes, kh, iso, maxit, ws, lay, tr, red, path);
+        return run_forward_generic(ln, y, x_out, M, N, planes, kh, iso, maxit, ws, lay, tr, red, path, br);
     }
     if (path == ADMM_PATH_FUSED) {
         // one workgroup per plane runs all K iterations (plane_kernel.hip); lane-native H^T y in
         // spec0, lane-native s in sA -- or, recording a trajectory, s_k in its own slot of tr.s
         namespace pk = admm::plane;
         void* ptab = ws + lay.F;
-        if (tables) rc = ln.run(ADMM_K_SETUP, [&] { return pk::launch_tables(Ct, Gt, ptab, s); });
+        if (tables) rc = ln.run(ADMM_K_SETUP, [&] {
+            if (grp) return pk::launch_tables_grouped(Ct, Gt, ptab, pk::grouped_count(br), br.tab_f, s);
+            return pk::launch_tables(Ct, Gt, ptab, s);
+        });
         if (rc) return rc;
+        // a grouped solve: the same descriptor over the lane-native table blocks
+        Branches bf = br;
+        bf.tab_f = (unsigned)(pk::grouped_tables_bytes() / 4);
         rc = ln.run(ADMM_K_PLANE, [&] {
             return pk::launch_plane(y, x_out, ptab, kh > 0, spec0, reinterpret_cast<float4*>(sbuf[0]), prm, maxit,
-                                   planes, s, tr.m ? nullptr : reinterpret_cast<float4*>(tr.s), nullptr, tr.m);
+                                   planes, s, tr.m ? nullptr : reinterpret_cast<float4*>(tr.s), grp ? &bf : nullptr, tr.m);
         });
         return rc;
     }
@@ -376,7 +414,7 @@ int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t
     if (rc) return rc;
     rc = ln.run(ADMM_K_PREP, [&] {
         return launch_column(N, 5, gc, clds, s, spec0, spec1, Ct, kh > 0 ? Gt : nullptr, twN, L, KB,
-                             kh > 0 ? (float)MN : 1.0f, nullptr, nullptr, kOneSolve, yh);
+                             kh > 0 ? (float)MN : 1.0f, nullptr, nullptr, br, yh);
     });
     if (rc) return rc;
     {
@@ -388,7 +426,7 @@ int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t
         float2* vsave = tr.v ? tr.v + (size_t)(it - 1) * np * N * L : nullptr;
         rc = ln.run(ADMM_K_COLUMN, [&] {
             return launch_column(N, vsave ? 7 : 6, gc, clds, s, spec0, spec1, Ct, Gt, twN, L, KB, 1.0f, vsave, nullptr,
-                                 kOneSolve, yh);
+                                 br, yh);
         });
         if (rc) return rc;
         if (it < maxit && !iso) {
@@ -403,7 +441,7 @@ int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t
             }
             rc = ln.run(ADMM_K_LINE, [&] {
                 return launch_line(L, Tu, dim3(N / Tu, (unsigned)np), llds, s, spec1, spec0, so, sn, nullptr, twM, N, prm,
-                            it == 1 ? 1 : 0, nTu);
+                            it == 1 ? 1 : 0, nTu, br);
             });
         } else if (it < maxit) {
             // isotropic: s is written in place (no halo reads of s in ISO_A); with a trajectory each
@@ -453,7 +491,7 @@ int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t
 
 int run_forward_generic(Launcher& ln, const float* y, float* x_out, int M, int N, size_t planes, int kh,
                         int iso, int maxit, unsigned char* ws, const Layout& lay,
-                        const Traj& tr, const admm_batch_reducer* red, int path) {
+                        const Traj& tr, const admm_batch_reducer* red, int path, const Branches& br) {
     namespace g = admm::gen;
     hipStream_t s = ln.s;
     int rc = ADMM_OK;
@@ -484,8 +522,10 @@ int run_forward_generic(Launcher& ln, const float* y, float* x_out, int M, int N
     set_lds(g::column_kernel, lcol);
     // compile-time-plan kernels where this build has the length (admm_smooth.hip): the column pass needs
     // N, the line passes M
-    const bool smc = opt(ADMM_OPT_SMOOTH) != 0 && admm::sm::has_length(N);
-    const bool sml = opt(ADMM_OPT_SMOOTH) != 0 && admm::sm::has_length(M);
+    // (a grouped solve runs the runtime-length kernels only: they take the group offsets)
+    const bool smooth = opt(ADMM_OPT_SMOOTH) != 0 && br.nbr != 0;
+    const bool smc = smooth && admm::sm::has_length(N);
+    const bool sml = smooth && admm::sm::has_length(M);
     auto line_fwd = [&](const float* src, float2* dst) {
         return ln.run(ADMM_K_PREP, [&] {
             if (sml) return admm::sm::launch_line_fwd(M, N, planes, s, src, dst, twM);
@@ -504,7 +544,7 @@ int run_forward_generic(Launcher& ln, const float* y, float* x_out, int M, int N
         if (rc) return rc;
         rc = ln.run(ADMM_K_PREP, [&] {
             hipLaunchKernelGGL(g::column_kernel, gc, dim3(256), lcol, s, spec0, spec1, Ct, Gt, twN, pN, H, KB, 32 | 1,
-                               kh > 0 ? (float)MN : 1.0f, (float2*)nullptr, (double*)nullptr, yh);
+                               kh > 0 ? (float)MN : 1.0f, (float2*)nullptr, (double*)nullptr, yh, br);
             return 0;
         });
         if (rc) return rc;
@@ -547,7 +587,7 @@ int run_forward_generic(Launcher& ln, const float* y, float* x_out, int M, int N
             if (smc && !vsave)
                 return admm::sm::launch_column(M, N, planes, s, spec0, spec1, Ct, Gt, twN, 1.0f, 0, opt(ADMM_OPT_SMOOTH), yh);
             hipLaunchKernelGGL(g::column_kernel, gc, dim3(256), lcol, s, spec0, spec1, Ct, Gt, twN, pN, H, KB,
-                               (vsave ? 4 : 0) | 16, 1.0f, vsave, (double*)nullptr, yh);
+                               (vsave ? 4 : 0) | 16, 1.0f, vsave, (double*)nullptr, yh, br);
             return 0;
         });
         if (rc) return rc;
@@ -569,7 +609,7 @@ int run_forward_generic(Launcher& ln, const float* y, float* x_out, int M, int N
             rc = ln.run(ADMM_K_LINE, [&] {
                 if (sml) return admm::sm::launch_line_upd(M, N, planes, s, xg, so, sn, nullptr, spec0, twM, prm, it == 1 ? 1 : 0);
                 hipLaunchKernelGGL(g::line_upd_kernel, gl, dim3(256), lup, s, xg, so, sn, (const float*)nullptr, spec0, twM,
-                                   pM, N, T, prm, it == 1 ? 1 : 0);
+                                   pM, N, T, prm, it == 1 ? 1 : 0, br);
                 return 0;
             });
             if (rc) return rc;

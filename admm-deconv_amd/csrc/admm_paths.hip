@@ -203,6 +203,17 @@ PathPlan plan_paths(const PathIn& q) {
     return pl;
 }
 
+// Grouped solve (a PSF, lambda and rho per image or channel): the kernels that take the plane -> group map.
+// 256 x 256 anisotropic from the fused kernel's plane count on: plane256_kernel over per-group lane-native tables;
+// the other tuned shapes (and 256 x 256 below the rule, or isotropic): the 2-pass kernels; every other shape: the
+// runtime-length kernels.  The smooth-length, CU-resident and fused isotropic kernels take one table set only.
+int plan_grouped(int M, int N, bool iso, size_t planes) {
+    if (generic_shape(M, N)) return ADMM_PATH_RUNTIME;
+    const PathIn q{M, N, iso, true, ADMM_MODE_FORWARD, 0, false, false, planes};
+    if (fused_shape(M, N, iso) && fused_enabled() && enough_planes(q, kMinFused)) return ADMM_PATH_FUSED;
+    return iso ? ADMM_PATH_2PASS_ISO : ADMM_PATH_2PASS;
+}
+
 // lines per block: the largest of 8, 4, 2, 1 dividing N with T * M <= 4096 (LDS ~ 24 T M bytes)
 // options ADMM_OPT_GEN_TM (max T x M of a line block), ADMM_OPT_GEN_KN (max KB x N of a column block)
 int gen_opt(int k, int dflt) {
@@ -277,6 +288,16 @@ int admm_query_forward_schedule(int M, int N, int iso, int kh, long long planes,
     const ChunkPlan cp = forward_chunks(M, N, (size_t)planes, iso != 0, pl.fwd);
     *chunk_planes = (long long)std::min(cp.chunk, (size_t)planes);
     *streams = cp.streams;
+    return ADMM_OK;
+}
+
+int admm_query_grouped_path(int M, int N, int iso, int kh, long long planes, int groups, int* fwd_path) {
+    if (!fwd_path) return fail(ADMM_E_INVALID, "admm_query_grouped_path: NULL output");
+    const int rc = check_shape(M, N, 1, 1, kh, kh > 0 ? 1 : 0, iso);   // (kw is not given: any kw <= N)
+    if (rc) return rc;
+    if (planes < 0 || groups < 1 || (planes > 0 && groups > planes))
+        return fail(ADMM_E_INVALID, "admm_query_grouped_path: planes must be >= 0 and 1 <= groups <= planes");
+    *fwd_path = plan_grouped(M, N, iso != 0, (size_t)planes);
     return ADMM_OK;
 }
 

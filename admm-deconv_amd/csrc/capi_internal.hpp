@@ -219,12 +219,31 @@ size_t multi_F_bytes();
 size_t multi_iso_rows(int K);
 admm::plane::Branches multi_branches(int P, int B, int nbr);
 
+// ---- grouped solve (admm_tvd_forward_grouped_dev_f32) ----
+// One path decision (admm_paths.hip): the fused kernel at 256 x 256 anisotropic from the plane-count rule, the
+// 2-pass kernels at the other tuned shapes, the runtime-length kernels elsewhere (never the smooth-length, resident
+// or fused isotropic kernels, never the MALL chunk schedule).
+int plan_grouped(int M, int N, bool iso, size_t planes);
+// Workspace: the single-PSF forward layout of the whole batch, and behind it G consecutive blocks of each table
+// (tab_f floats of C, tab_f float2 of G and grouped_tables_bytes() of lane-native tables per group; one 16-byte scalar
+// block per group).  The layout's own scalar / C / G / lane-native slots stay allocated and are not used (one table
+// set, about 0.8 MB at 256 x 256); `f` names the appended blocks instead.
+struct GroupedLayout {
+    Layout f;          // prm, C, G, F point at group 0's blocks
+    unsigned tab_f;    // floats (C) / float2 (G) between the groups' 2-pass tables
+    size_t total;
+};
+GroupedLayout make_grouped_layout(int M, int N, size_t planes, int groups, bool psf, bool iso);
+
 // ---- launch sequencing (admm_launch.hip) ----
+// grp (run_forward): a grouped solve -- h holds one PSF per group, sc.lam / sc.rho point at nparam device values
+// (grp->prm_f = 0: one pair), lay is a GroupedLayout's; the setup kernels run over the groups
 // tables = false: the workspace already holds this call's twiddles, C / G tables and scalar block (a later plane
 // chunk of the same call through the same chunk workspace): the setup kernels are not launched again
 int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t planes, const float* h, int kh,
                 int kw, const admm::ScalarSrc& sc, int iso, int maxit, unsigned char* ws, const Layout& lay,
-                const Traj& tr, const admm_batch_reducer* red, int fwd_path, bool tables = true);
+                const Traj& tr, const admm_batch_reducer* red, int fwd_path, bool tables = true,
+                const admm::plane::Branches* grp = nullptr);
 // everything run_backward does after validating the call and updating the recordings registry
 int launch_backward(int phases, const float* y, const float* x_bar, float* y_bar, float* h_bar, float* lambda_bar,
                     float* rho_bar, int M, int N, size_t planes, const float* h, int kh, int kw,

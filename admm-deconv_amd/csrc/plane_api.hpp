@@ -19,25 +19,46 @@ constexpr int kPlaneM = 256, kPlaneN = 256;
 // input (the denoiser, src/nets/net_build.jl:113-125).  Grid plane q is plane q % ppb of the shared input,
 // solved with branch i = q / ppb's tables and scalars; its output goes to the chcat position of branch i
 // (image b, channel i * P + p of a (B, nbr * P, N, M) tensor).  A single solve is nbr = 1.
+// nbr = 0 is a grouped solve (admm_tvd_forward_grouped_dev_f32): every grid plane is its own input and output
+// plane, and plane (b, p) = b * P + p takes the tables and scalars of group i = b * gmul_b + p * gmul_p.
 struct Branches {
     int ppb;          // planes per branch (B * P)
     int nbr;          // branches
     int P;            // channels per image of one branch
     unsigned tab_f;   // floats between the branches' lane-native table blocks (tables_bytes() / 4)
     unsigned prm_f;   // floats between the branches' {tau, rho, lambda} blocks
+    int gmul_b;       // grouped solve: groups between consecutive images (gb > 1 ? gp : 0)
+    int gmul_p;       // grouped solve: groups between consecutive channels (gp > 1 ? 1 : 0)
 };
+// descriptor of a grouped solve over (B, P) planes in gb x gp groups (gb in {1, B}, gp in {1, P})
+inline Branches grouped_branches(int P, int B, int gb, int gp, unsigned tab_f, unsigned prm_f) {
+    return Branches{P * B, 0, P, tab_f, prm_f, gb > 1 ? gp : 0, gp > 1 ? 1 : 0};
+}
 // Where grid plane q reads and writes (above).  The 2-pass kernels (admm_kernels.hip) take the same struct, with
 // tab_f = floats between the branches' 2-pass C tables.
 struct BranchOf {
     int i;
     size_t in_plane, out_plane;
 };
+// groups of a grouped descriptor (the last plane's group index + 1)
+inline int grouped_count(const Branches& br) { return (br.ppb / br.P - 1) * br.gmul_b + (br.P - 1) * br.gmul_p + 1; }
 __host__ __device__ inline BranchOf branch_of(const Branches& br, size_t plane) {
     if (br.nbr == 1) return {0, plane, plane};
     const int i = (int)(plane / (size_t)br.ppb);
     const size_t loc = plane - (size_t)i * br.ppb;
     const size_t b = loc / (size_t)br.P, p = loc - b * br.P;
     return {i, loc, (b * br.nbr + i) * br.P + p};
+}
+// A grouped solve's descriptor (nbr = 0) goes to the kernels' GRP instantiations only, which look the plane up here;
+// the existing instantiations keep branch_of and their code.
+__host__ __device__ inline int group_of(const Branches& br, size_t plane) {
+    const size_t b = plane / (size_t)br.P, p = plane - b * br.P;
+    return (int)b * br.gmul_b + (int)p * br.gmul_p;
+}
+template <bool GRP>
+__host__ __device__ inline BranchOf plane_of(const Branches& br, size_t plane) {
+    if constexpr (GRP) return {group_of(br, plane), plane, plane};
+    else return branch_of(br, plane);
 }
 constexpr int kTabEntries = 2 * 32 * 512;   // lane-native spectral table entries (= 256 x 128)
 
@@ -52,6 +73,11 @@ inline size_t hty_bytes(size_t planes) { return planes * kHtyStrideF2 * 8; }
 
 // Cf/C0b/Gf/G0b from the 2-pass tables Ct/Gt (Gt may be NULL: no PSF)
 hipError_t launch_tables(const float* Ct, const float2* Gt, void* tables, hipStream_t s);
+// a grouped solve's `groups` table blocks, grouped_tables_bytes() apart, from 2-pass tables ct_f floats (Ct) /
+// float2 (Gt) apart
+inline size_t grouped_tables_bytes() { return (tables_bytes() + 255) & ~size_t(255); }
+hipError_t launch_tables_grouped(const float* Ct, const float2* Gt, void* tables, int groups, unsigned ct_f,
+                                 hipStream_t s);
 
 // all K >= 1 iterations for `planes` planes of 256 x 256; hln: planes x 256 KiB, sln: planes x 512 KiB
 // traj != NULL: record s_1..s_{K-1} for the adjoint, slot k-1 at traj + (k-1) * planes * 64 * 512

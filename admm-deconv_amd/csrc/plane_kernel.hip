@@ -144,9 +144,9 @@ __device__ __forceinline__ void pin_regs(float2 (&S)[64]) {
 // kj*(M/2+1) + k).  Entry ((half*4 + i)*8 + q2)*512 + t is the multiplier thread t applies to bin
 // kj = q + 8 i + 32 q2 (q = t & 7) of spectral column k = 32 half + (c >> 1) + 64 (c & 1), c = t >> 3.
 // Column 0 (packed X[0] / X[M/2] pair): Cf = (c0 + cL)/2 and C0b[kj] = (c0 - cL)/2 (same for G).
-__global__ __launch_bounds__(256) void tables_kernel(const float* __restrict__ Ct, const float2* __restrict__ Gt,
-                                                     float* __restrict__ Cf, float* __restrict__ C0b,
-                                                     float2* __restrict__ Gf, float2* __restrict__ G0b) {
+__device__ __forceinline__ void tables_body(const float* __restrict__ Ct, const float2* __restrict__ Gt,
+                                            float* __restrict__ Cf, float* __restrict__ C0b,
+                                            float2* __restrict__ Gf, float2* __restrict__ G0b) {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= kTab) return;
     const int t = idx & 511, q2 = (idx >> 9) & 7, i = (idx >> 12) & 3, half = idx >> 14;
@@ -168,7 +168,11 @@ __global__ __launch_bounds__(256) void tables_kernel(const float* __restrict__ C
         if (Gt) Gf[idx] = Gt[kj * H + k];
     }
 }
-
+__global__ __launch_bounds__(256) void tables_kernel(const float* __restrict__ Ct, const float2* __restrict__ Gt,
+                                                     float* __restrict__ Cf, float* __restrict__ C0b,
+                                                     float2* __restrict__ Gf, float2* __restrict__ G0b) {
+    tables_body(Ct, Gt, Cf, C0b, Gf, G0b);
+}
 // One half of the column phase: spectral columns k with register m in [32 HALF, 32 HALF + 32).
 // MODE 0: real multiplier Cf (x-update); MODE 1: complex multiplier Gf (H^T y).
 template <int MODE, int HALF>
@@ -527,7 +531,8 @@ __device__ __forceinline__ void dbg_dump(float2* dbg, const float2 (&S)[64], int
 // TRAJ 2: record the ST mask bits of s_k instead (mask_byte): s stays in place in sln as in the plain solve,
 // and iteration k writes its mask slot k-1 (mtraj + (k-1) * mslot dwords, plane p at p * 16 * 512).
 // br: several branches in one grid (Branches; nbr = 1 is a single solve).
-template <bool PSF, int DBG = 0, int TRAJ = 0>
+// GRP: a grouped solve (br.nbr = 0): plane q reads and writes plane q with the tables and scalars of group_of(q).
+template <bool PSF, int DBG = 0, int TRAJ = 0, bool GRP = false>
 __global__ __launch_bounds__(kPT) void plane256_kernel(const float* __restrict__ y, float* __restrict__ x_out,
                                                        const float* __restrict__ Cf, const float* __restrict__ C0b,
                                                        const float2* __restrict__ Gf, const float2* __restrict__ G0b,
@@ -535,7 +540,7 @@ __global__ __launch_bounds__(kPT) void plane256_kernel(const float* __restrict__
                                                        float4* __restrict__ traj = nullptr, size_t traj_slot = 0,
                                                        Branches br = Branches{1, 1, 1, 0u, 0u},
                                                        unsigned* __restrict__ mtraj = nullptr, size_t mslot = 0) {
-    const BranchOf bo = branch_of(br, blockIdx.x);
+    const BranchOf bo = plane_of<GRP>(br, blockIdx.x);
     Cf += (size_t)bo.i * br.tab_f;
     C0b += (size_t)bo.i * br.tab_f;
     Gf = reinterpret_cast<const float2*>(reinterpret_cast<const float*>(Gf) + (size_t)bo.i * br.tab_f);

@@ -44,12 +44,20 @@ static void launch_one(const float* y, float* x_out, const Tables& t, float2* hl
                        planes * 64 * kPT, br, masks, planes * 16 * kPT);
 }
 
+static hipError_t launch_plane_grouped(const float* y, float* x_out, const void* tables, bool psf, float2* hln,
+                                       float4* sln, const float* prm, int K, size_t planes, hipStream_t s,
+                                       const Branches& br);
+
 hipError_t launch_plane(const float* y, float* x_out, const void* tables, bool psf, float2* hln, float4* sln,
                         const float* prm, int K, size_t planes, hipStream_t s, float4* traj,
                         const Branches* brp, unsigned* masks) {
     const Tables t = carve(tables);
     const Branches br = brp ? *brp : one_branch();
     const int mode = traj ? 1 : masks ? 2 : 0;
+    if (br.nbr == 0) {   // a grouped solve (forward only)
+        if (mode != 0) return hipErrorInvalidValue;
+        return launch_plane_grouped(y, x_out, tables, psf, hln, sln, prm, K, planes, s, br);
+    }
 #define X(P, M)                                                                                     \
     if (psf == P && mode == M) {                                                                    \
         launch_one<P, M>(y, x_out, t, hln, sln, prm, K, planes, s, traj, br, masks);               \
@@ -138,6 +146,48 @@ hipError_t launch_iso_radj(const float2* rpart, float2* Rmap, const float2* nrm1
     const Branches br = brp ? *brp : Branches{(int)planes, 1, 1, 0u, 0u};
     hipLaunchKernelGGL(iso_radj_kernel, dim3(64 * kPT / 64, (unsigned)br.nbr), dim3(256), 0, s, rpart, Rmap, nrm1, part,
                        part_branch, prm, br);
+    return hipGetLastError();
+}
+
+// ---- grouped solve ----
+// Its kernels are defined and instantiated last: the device code of the kernels above keeps its place in the
+// code object whether or not these exist.
+// a grouped solve's table blocks: block row g from group g's 2-pass tables (ct_f floats / float2 apart) into its
+// lane-native block (tab_f floats apart, as plane256_kernel offsets them).
+__global__ __launch_bounds__(256) void tables_grouped_kernel(const float* __restrict__ Ct, const float2* __restrict__ Gt,
+                                                             float* __restrict__ Cf, float* __restrict__ C0b,
+                                                             float2* __restrict__ Gf, float2* __restrict__ G0b,
+                                                             unsigned ct_f, unsigned tab_f) {
+    const size_t g = blockIdx.y, o = g * tab_f;
+    tables_body(Ct + g * ct_f, Gt ? Gt + g * ct_f : nullptr, Cf + o, C0b + o,
+                reinterpret_cast<float2*>(reinterpret_cast<float*>(Gf) + o),
+                reinterpret_cast<float2*>(reinterpret_cast<float*>(G0b) + o));
+}
+
+hipError_t launch_tables_grouped(const float* Ct, const float2* Gt, void* tables, int groups, unsigned ct_f,
+                                 hipStream_t s) {
+    const Tables t = carve(tables);
+    hipLaunchKernelGGL(tables_grouped_kernel, dim3(kTab / 256, (unsigned)groups), dim3(256), 0, s, Ct, Gt, t.Cf, t.C0b,
+                       t.Gf, t.G0b, ct_f, (unsigned)(grouped_tables_bytes() / 4));
+    return hipGetLastError();
+}
+
+template <bool PSF>
+static void launch_one_grouped(const float* y, float* x_out, const Tables& t, float2* hln, float4* sln, const float* prm,
+                               int K, size_t planes, hipStream_t s, const Branches& br) {
+    (void)hipFuncSetAttribute((const void*)plane256_kernel<PSF, 0, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)kLdsBytes);
+    hipLaunchKernelGGL((plane256_kernel<PSF, 0, 0, true>), dim3((unsigned)planes), dim3(kPT), kLdsBytes, s, y, x_out,
+                       t.Cf, t.C0b, t.Gf, t.G0b, hln, sln, prm, K, nullptr, nullptr, planes * 64 * kPT, br, nullptr,
+                       planes * 16 * kPT);
+}
+
+static hipError_t launch_plane_grouped(const float* y, float* x_out, const void* tables, bool psf, float2* hln,
+                                       float4* sln, const float* prm, int K, size_t planes, hipStream_t s,
+                                       const Branches& br) {
+    const Tables t = carve(tables);
+    if (psf) launch_one_grouped<true>(y, x_out, t, hln, sln, prm, K, planes, s, br);
+    else launch_one_grouped<false>(y, x_out, t, hln, sln, prm, K, planes, s, br);
     return hipGetLastError();
 }
 

@@ -231,6 +231,40 @@ int admm_tvd_backward_multi_recorded_dev_f32(const float* x_bar, float* y_bar, f
                                              int maxit, const float* x_out, void* workspace,
                                              size_t workspace_bytes, void* stream);
 
+/* Grouped solve: a PSF, lambda and rho per image or per channel in ONE call (tiles under spatially varying blur,
+ * per-image motion kernels, per-channel PSFs for chromatic aberration, per-image noise levels; the reference builds
+ * such layers side by side, net_build.jl:102-110, and its constructors take `groups`, deconv_admm.jl:37,47).
+ * y, x_out: `float[B][P][N][M]` as everywhere.  The B*P planes fall into G = gb * gp groups, gb in {1, B}, gp in
+ * {1, P}: plane (b, p) belongs to group g = (gb > 1 ? b : 0) * gp + (gp > 1 ? p : 0) -- one PSF for all planes
+ * (G = 1), one per image, one per channel, or one per plane.
+ * h: `float[G][kw][kh]`, one PSF per group, all of one kh x kw (centring, padding and adjoint convention per group
+ * exactly as in admm_tvd_forward_f32, ops.jl:71-81); kh = kw = 0: no PSF for any group (h is ignored).
+ * lambda, rho: device arrays of nparam floats read on the device (no host sync): nparam = G gives group g the pair
+ * (lambda[g], rho[g]), nparam = 1 one pair for all groups.
+ * iso = 0: every plane is the solve of that plane alone with its group's h, lambda, rho -- bitwise the result of
+ * the single-PSF call through the same kernels.  iso = 1: the reference's batch coupling is kept: the pixel norm
+ * sums over ALL planes of the call, whatever their group (ops.jl:6), while each plane's x-update uses its own group's
+ * C and H^T y; the BT factor is one map per batch, so an isotropic call takes nparam = 1 (nparam = G > 1:
+ * ADMM_E_UNSUPPORTED).  There is no sharded (reducer) form.
+ * Limits: shapes as admm_tvd_forward_f32 (2..4096 per side, kh <= M, kw <= N); at most 65,280 planes per call (no
+ * internal chunking); maxit = 0 returns zeros.  ADMM_E_INVALID: gb not in {1, B}, gp not in {1, P}, nparam not in
+ * {1, G}, NULL lambda / rho, NULL h with kh > 0.  Asynchronous on `stream`, allocates nothing, deterministic, never
+ * modifies y.  The workspace (256-byte aligned, admm_tvd_grouped_workspace_bytes) is the single-PSF forward's plus
+ * one table set and one scalar block per group.
+ * Paths (admm_query_grouped_path; host only, as admm_query_paths; `groups` is validated, the decision does not
+ * depend on it): ADMM_PATH_FUSED at 256 x 256 anisotropic from the fused kernel's plane count (ADMM_OPT_MIN_PLANES),
+ * with per-group lane-native tables; ADMM_PATH_2PASS / _2PASS_ISO at the other power-of-two shapes (and 256 x 256
+ * below the rule or isotropic); ADMM_PATH_RUNTIME for every other shape, both proxes.  NOT taken by grouped calls:
+ * the smooth-length, CU-resident and fused isotropic kernels (their shapes run the runtime-length or 2-pass
+ * kernels) and the MALL chunk schedule (a grouped call runs on the caller's stream only). */
+int admm_tvd_grouped_workspace_bytes(int M, int N, int P, int B, int gb, int gp, int kh, int kw, int iso,
+                                     size_t* out_bytes);
+int admm_tvd_forward_grouped_dev_f32(const float* y, float* x_out, int M, int N, int P, int B, int gb, int gp,
+                                     const float* h, int kh, int kw, const float* lambda, const float* rho,
+                                     int nparam, int iso, int maxit, void* workspace, size_t workspace_bytes,
+                                     void* stream);
+int admm_query_grouped_path(int M, int N, int iso, int kh, long long planes, int groups, int* fwd_path);
+
 /* Library options: process-global switches read at each call.  The defaults are the tuned choices;
  * the others exist for tests (fused vs 2-pass paths) and tuning experiments.  Not read from the
  * environment.  A recording remembers the options it was made with (see above). */
