@@ -1,9 +1,17 @@
-// admm_launch.hip -- launch sequencing of the ADMM solve (see capi_internal.hpp): the 2-pass kernels
-//   SETUP  (twiddles + C, ops.jl:22-37)
-//   PREP   (H^T y once + first line rFFT, ops.jl:71-81 / :168 first iteration)
-//   K x COLUMN, (K-1) x LINE, 1 x FINAL                (ops.jl:166-174)
-// and the fused / CU-resident / runtime-length paths and reverse sweeps, enqueued on the caller's stream
+// admm_launch.hip -- launch sequencing of the ADMM solve (see capi_internal.hpp), enqueued on the caller's stream
 // exactly as plan_paths (admm_paths.hip) decided.  Reference: /root/reference/src/ops/ops.jl:99-188.
+//   template dispatch    the instantiation list of the 2-pass kernels (its order is the code object's layout)
+//   workspace views      a Layout / BwdLayout / MultiLayout resolved into typed pointers once
+//   shared steps         the natural-layout isotropic norm, the s slots of an iteration, the spectral convolution
+//   TwoPass              one 2-pass grid -- a single or grouped solve, or several branches in one grid -- and the
+//                        two sequences every caller runs on it:
+//     two_pass_forward   PREP (Y_h = F(H^T y): line transform, column x conj(Sigma_c), ops.jl:71-81), K x COLUMN,
+//                        (K-1) x LINE (or ISO_A, norm, ISO_B), 1 x FINAL                        (ops.jl:166-174)
+//     two_pass_reverse   line transform of x_bar, then per step COLUMN and the line adjoint (or ISO_ADJ_A, _R, _B)
+//   run_forward          SETUP (twiddles + C, ops.jl:22-37), then the fused / CU-resident / 2-pass path
+//   run_forward_generic  the runtime-length path (its own kernels: a separate inverse, the smooth-length alternatives)
+//   launch_backward      recording forward, one reverse sweep (fused, fused isotropic, runtime-length, 2-pass), assembly
+//   launch_*_multi       the one-grid multi-branch solve: the fused kernels, or the same TwoPass sequences
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -24,7 +32,10 @@ namespace admm_capi {
 using namespace admm;
 
 // ---- template dispatch -----------------------------------------------------------------------
-using namespace admm;
+// This translation unit alone compiles the 2-pass kernels, and they land in the code object in the order in which
+// the host code first names them: these dispatchers (and launch_line_adj / launch_iso_adj_a / launch_iso_adj_b
+// further down) are that instantiation list.  Their order fixes the code object's layout, and code placement
+// alone is measurable (0.8 % at c2): keep them where they are and in this order.
 
 template <typename K>
 void set_lds(K kernel, size_t lds) {
@@ -211,10 +222,6 @@ admm::gen::FPlan make_fplan(int n) {
     return p;
 }
 
-int run_forward_generic(Launcher& ln, const float* y, float* x_out, int M, int N, size_t planes, int kh,
-                        int iso, int maxit, unsigned char* ws, const Layout& lay,
-                        const Traj& tr, const admm_batch_reducer* red, int path, const Branches& br = kOneSolve);
-
 // the caller's cross-shard sum of an M x N map (isotropic prox over a sharded batch)
 int call_reducer(const admm_batch_reducer* red, float* buf, size_t count, hipStream_t s) {
     const int r = red->fn(buf, count, reinterpret_cast<void*>(s), red->user);
@@ -222,46 +229,345 @@ int call_reducer(const admm_batch_reducer* red, float* buf, size_t count, hipStr
     return ADMM_OK;
 }
 
+// ---- workspace views: a layout's offsets resolved into typed pointers once ----------------------------------
+template <typename T>
+T* at(unsigned char* ws, size_t off) {
+    return reinterpret_cast<T*>(ws + off);
+}
+
+struct FwdView {
+    float2 *twM, *twN;
+    float* C;
+    float2* G;     // null without a PSF
+    float* prm;    // tau = lambda / rho (ops.jl:20), rho, lambda
+    float* hty;    // H^T y -- or, on the 2-pass and runtime-length paths, Y_h = F(H^T y) (float2, see yh())
+    float* s[2];
+    float2 *spec0, *spec1;
+    float *fmap, *part, *xg;   // isotropic f map and plane-group partials; runtime-length x
+    void* F;                   // lane-native tables (256 x 256)
+    float2* yh() const { return reinterpret_cast<float2*>(hty); }
+};
+FwdView view(unsigned char* ws, const Layout& l, bool psf) {
+    return FwdView{at<float2>(ws, l.twM), at<float2>(ws, l.twN), at<float>(ws, l.C), psf ? at<float2>(ws, l.G) : nullptr,
+                   at<float>(ws, l.prm), at<float>(ws, l.hty), {at<float>(ws, l.sA), at<float>(ws, l.sB)},
+                   at<float2>(ws, l.spec0), at<float2>(ws, l.spec1), at<float>(ws, l.fmap), at<float>(ws, l.part),
+                   at<float>(ws, l.xg), ws + l.F};
+}
+
+// what a reverse sweep reads and writes besides the forward view's tables and spectra
+struct SweepBufs {
+    const float* traj;   // s_k slots (natural layout; the 2-pass line adjoint also reads the fused kernel's)
+    const float* nrm;    // |s_k| slots (isotropic)
+    float2* v;           // h_bar: the recorded dim-2 spectra and the planes' Q accumulators, else both null
+    double* Qp;
+    float* sb[2];        // sbar ping-pong
+    float* vsum;         // Vsum = sum_k vbar_k (null: neither y_bar nor h_bar wanted)
+    float *wbar, *Rmap, *Rpart;   // isotropic
+    double* part;        // (rho_bar, tau_bar) partial rows
+    const float* xK;     // the forward's output: enters rho_bar only (null without it)
+};
+
+struct BwdView {
+    FwdView f;
+    SweepBufs b;
+    double2* sig;
+    double *Q, *hpart, *hcorr, *hA, *rt, *rtmp;
+};
+BwdView view(unsigned char* ws, const BwdLayout& l, bool psf, bool iso, bool want_h, bool want_v, const float* xK) {
+    BwdView v{view(ws, l.f, psf)};
+    v.b = SweepBufs{at<float>(ws, l.traj_s), iso ? at<float>(ws, l.traj_n) : nullptr,
+                    want_h ? at<float2>(ws, l.traj_v) : nullptr, want_h ? at<double>(ws, l.Qp) : nullptr,
+                    {at<float>(ws, l.sbA), at<float>(ws, l.sbB)}, want_v ? at<float>(ws, l.vsum) : nullptr,
+                    iso ? at<float>(ws, l.wbar) : nullptr, iso ? at<float>(ws, l.Rmap) : nullptr,
+                    iso ? at<float>(ws, l.Rpart) : nullptr, at<double>(ws, l.rpart), xK};
+    v.sig = want_h ? at<double2>(ws, l.sig) : nullptr;
+    v.Q = at<double>(ws, l.Q);
+    v.hpart = at<double>(ws, l.hpart);
+    v.hcorr = psf ? at<double>(ws, l.hcorr) : nullptr;
+    v.hA = want_h ? at<double>(ws, l.hA) : nullptr;
+    v.rt = at<double>(ws, l.rt);
+    v.rtmp = at<double>(ws, l.rtmp);
+    return v;
+}
+
+// the one-grid call's slots that both of its grids (fused, 2-pass) use
+struct MultiView {
+    float* prm;
+    float2 *twM, *twN;
+    float2* hln;          // fused: lane-native H^T y, then each branch's Vsum; 2-pass: Y_h
+    unsigned char *sln, *traj, *sbar, *vsl;
+    float *fmap, *qpart, *nrm, *rmap;
+    double *part, *rt, *rtmp;
+};
+MultiView view(unsigned char* ws, const MultiLayout& l) {
+    return MultiView{at<float>(ws, l.prm), at<float2>(ws, l.twM), at<float2>(ws, l.twN), at<float2>(ws, l.hln),
+                     ws + l.sln, ws + l.traj, ws + l.sbar, ws + l.vsl, at<float>(ws, l.fmap), at<float>(ws, l.qpart),
+                     at<float>(ws, l.nrm), at<float>(ws, l.rmap), at<double>(ws, l.part), at<double>(ws, l.rt),
+                     at<double>(ws, l.rtmp)};
+}
+
+// ---- shared steps ---------------------------------------------------------------------------------------------
+// Natural-layout isotropic batch norm: the plane groups' (or planes') |s|^2 partials -> BT factor f (and |s| when
+// recording).  A sharded batch splits it into the shard sum, the caller's all-reduce of the M x N map and the factor.
+// ny branches (grid y), each with its own partials, maps and {tau, rho, lambda} block prm_f floats apart.
+int iso_norm_step(Launcher& ln, const float* part, float* fmap, int ngroups, size_t MN, const float* prm, float* nrm_out,
+                  const admm_batch_reducer* red, unsigned ny = 1, unsigned prm_f = 0) {
+    hipStream_t s = ln.s;
+    const int nb = (int)((MN + 63) / 64);   // 64 pixels per block (group_sum)
+    const dim3 gr(nb < 2048 ? nb : 2048, ny);
+    if (!red)
+        return ln.run(ADMM_K_NORM, [&] {
+            hipLaunchKernelGGL(admm::iso_r_kernel, gr, dim3(kThreads), 0, s, part, fmap, ngroups, MN, prm, nrm_out, prm_f);
+        });
+    int rc = ln.run(ADMM_K_NORM, [&] {
+        hipLaunchKernelGGL(admm::iso_sum_kernel, gr, dim3(kThreads), 0, s, part, fmap, ngroups, MN);
+    });
+    if (rc) return rc;
+    rc = call_reducer(red, fmap, MN, s);
+    if (rc) return rc;
+    return ln.run(ADMM_K_NORM, [&] {
+        hipLaunchKernelGGL(admm::iso_fin_kernel, gr, dim3(kThreads), 0, s, fmap, MN, prm, nrm_out);
+    });
+}
+
+// Iteration it = 1 .. K-1 reads s_{it-1} and writes s_it: a recording keeps s_it in trajectory slot it - 1; without
+// one the two buffers take turns (isotropic: b1 = b0, s is updated in place).  Iteration 1 reads no s (the kernels'
+// s_zero / first flag): so is then sn itself, any valid pointer would do.
+struct Slots {
+    const float* so;
+    float* sn;
+};
+Slots fwd_slots(int it, float* traj, size_t sstride, float* b0, float* b1) {
+    float* sn = traj ? traj + (size_t)(it - 1) * sstride : (it & 1) ? b0 : b1;
+    if (it == 1) return {sn, sn};
+    return {traj ? traj + (size_t)(it - 2) * sstride : (it & 1) ? b1 : b0, sn};
+}
+
+// ---- one 2-pass grid ------------------------------------------------------------------------------------------
+// Grid plane q of several branches in one grid is branch i's solve of input plane loc (q = i ppb + loc; y shared,
+// x_out / x_bar in the chcat layout: the first and last line transform map planes, admm_kernels.hip PlaneMap); per
+// branch its C table, {tau, rho, lambda}, f map, |s| slots, R map, plane groups and partial rows.
+struct TwoPass {
+    Launcher& ln;
+    int M, N, L, T, KB;
+    int Tu, nTu;               // the update kernel's lines and threads per block (512-point lines)
+    size_t planes, MN;
+    dim3 gl, gc, gu;           // line transforms and adjoints, column pass, line update
+    size_t flds, clds, llds;
+    const float2 *twM, *twN;
+    const float* C;
+    const float2* G;
+    const float* prm;
+    float2 *spec0, *spec1, *yh;
+    Branches br;               // column pass and line update: one solve, a grouped solve, or the branches
+    Branches bro;              // every other kernel: one solve (a grouped solve too), or the branches
+    int map_in, map_out;       // plane maps of the first / last line transform
+    // isotropic: ng plane groups in all (ISO_A's grid y) of Gp planes, ngb per branch (ngb_k: the kernels' argument,
+    // 0 for one solve), gplanes planes per branch; the norm kernels' grid y and prm stride; floats per |s| slot
+    float *fmap, *qpart;
+    int ng, Gp, ngb, ngb_k, gplanes;
+    unsigned ny, prm_f;
+    size_t nstride;
+    // reverse sweep: partial rows per step, doubles between the branches' row blocks, ISO_ADJ_R's first row of a step
+    int rows;
+    size_t pbs;
+    int r_off;
+};
+
+TwoPass two_pass_grid(Launcher& ln, int M, int N, size_t planes, int T) {
+    TwoPass c{ln, M, N, M / 2, T, column_KB(M, N)};
+    // the per-iteration line update runs 4-line blocks at 512-point lines (its just-in-time loads let 4 of
+    // them share a CU, admm_kernels.hip line_kernel); the one-off line transforms keep T
+    // 512-point lines: 8-line update blocks of 512 threads (round 5, tools/c4_line_sweep.sh: line pass 1.217 ->
+    // 1.196 ms at c4; 4 lines x 256 threads was round 1's choice; 16 x 1024, 4 x 512 and 8 x 1024 slower:
+    // profiles/r05_c4_line_sweep.jsonl)
+    c.Tu = (M == 512 && T > 4) ? 8 : T;
+    c.nTu = (M == 512 && c.Tu == 8) ? 512 : kThreads;
+    c.planes = planes;
+    c.MN = (size_t)M * N;
+    c.gl = dim3(N / T, (unsigned)planes);
+    c.gc = dim3(c.L / c.KB, (unsigned)planes);
+    c.gu = dim3(N / c.Tu, (unsigned)planes);
+    c.flds = fwdinv_lds(M, T);
+    c.clds = column_lds(N, c.KB);
+    c.llds = line_lds(M, c.Tu);
+    return c;
+}
+
+// a single solve, or (grp) a grouped one: the descriptor of its C / G tables, tab_f apart, and scalar blocks
+TwoPass two_pass_single(Launcher& ln, int M, int N, size_t planes, int T, const FwdView& v, const Branches& grp = kOneSolve) {
+    TwoPass c = two_pass_grid(ln, M, N, planes, T);
+    c.twM = v.twM, c.twN = v.twN, c.C = v.C, c.G = v.G, c.prm = v.prm;
+    c.spec0 = v.spec0, c.spec1 = v.spec1, c.yh = v.yh();   // the workspace's H^T y slot holds Y_h on this path
+    c.br = grp, c.bro = kOneSolve;
+    c.map_in = c.map_out = kMapGrid;
+    c.fmap = v.fmap, c.qpart = v.part;
+    c.ng = c.ngb = iso_ngroups(planes), c.Gp = iso_group(planes), c.ngb_k = 0, c.gplanes = (int)planes;
+    c.ny = 1, c.prm_f = 0, c.nstride = c.MN;
+    return c;
+}
+
+// ---- several branches below the plane-count rule: the 2-pass kernels over every branch's planes ----
+Branches multi2_branches(int P, int B, int nbr) { return Branches{P * B, nbr, P, (unsigned)(multi_C_bytes() / 4), 4u}; }
+
+TwoPass two_pass_multi(Launcher& ln, int P, int B, int nbr, size_t planes, int T, unsigned char* ws, const MultiLayout& Ly) {
+    TwoPass c = two_pass_grid(ln, kMultiM, kMultiN, planes, T);
+    const MultiView v = view(ws, Ly);
+    c.twM = v.twM, c.twN = v.twN, c.C = at<float>(ws, Ly.C), c.G = nullptr, c.prm = v.prm;
+    // H^T y = y (no PSF) in the spectral domain: Y_h = F y per grid plane in the hln slot, unused by the 2-pass grid
+    c.spec0 = at<float2>(ws, Ly.spec0), c.spec1 = at<float2>(ws, Ly.spec1), c.yh = v.hln;
+    c.br = c.bro = multi2_branches(P, B, nbr);
+    c.map_in = kMapIn, c.map_out = kMapOut;
+    c.fmap = v.fmap, c.qpart = v.qpart;
+    c.ng = nbr * Ly.ngb, c.Gp = Ly.G, c.ngb = c.ngb_k = Ly.ngb, c.gplanes = P * B;
+    c.ny = (unsigned)nbr, c.prm_f = 4u, c.nstride = (size_t)nbr * c.MN;
+    c.rows = Ly.rows_b, c.pbs = Ly.pbs, c.r_off = Ly.nblk_a;
+    return c;
+}
+
+// dst = F^-1 [multiplier] F src, spectrally (mode 1: conj(Sigma_c), H^T; 2: Sigma_c, H; launch_column)
+int two_pass_conv(const TwoPass& c, int cls, int mode, const float* src, float* dst) {
+    Launcher& ln = c.ln;
+    hipStream_t s = ln.s;
+    int rc = ln.run(cls, [&] { return launch_line_fwd(c.L, c.T, c.gl, c.flds, s, src, c.spec0, c.twM, c.N); });
+    if (rc) return rc;
+    rc = ln.run(cls, [&] {
+        return launch_column(c.N, mode, c.gc, c.clds, s, c.spec0, c.spec1, c.C, c.G, c.twN, c.L, c.KB, 1.0f);
+    });
+    if (rc) return rc;
+    return ln.run(cls, [&] { return launch_line_inv(c.L, c.T, c.gl, c.flds, s, c.spec1, dst, c.twM, c.N); });
+}
+
+// PREP: Y_h = F(H^T y) = conj(Sigma_c) F y as a 2-D packed spectrum straight from F y (line transform, column
+// transform x conj(Sigma_c)), never H^T y in space: every iteration adds it to the spectrum of rho D^T w in
+// the column pass, so the per-iteration fp32 transforms carry only rho D^T w (x 16x, y_bar / h_bar ~2-9x closer
+// to the fp64 oracle than with H^T y added before the line transform; DESIGN.md s1 "H^T y in the spectrum").
+// Iteration 1 (w = 0) transforms a zero line spectrum and adds Y_h.  Then K x column, (K-1) x line update (isotropic:
+// ISO_A over the plane groups, the batch norm, ISO_B) and the final inverse.
+// tr: s_it into trajectory slot it - 1, the dim-2 spectrum of iteration it (before the multiply, h_bar) into slot
+// it - 1 of tr.v, |s_it| into norm slot it - 1; b0 / b1: the s buffers without a recording (fwd_slots).
+int two_pass_forward(const TwoPass& c, const float* y, float* x_out, int maxit, bool iso, const Traj& tr, float* b0,
+                     float* b1, const admm_batch_reducer* red = nullptr) {
+    Launcher& ln = c.ln;
+    hipStream_t s = ln.s;
+    int rc = ln.run(ADMM_K_PREP, [&] {
+        return launch_line_fwd(c.L, c.T, c.gl, c.flds, s, y, c.spec0, c.twM, c.N, c.bro, c.map_in);
+    });
+    if (rc) return rc;
+    rc = ln.run(ADMM_K_PREP, [&] {
+        return launch_column(c.N, 5, c.gc, c.clds, s, c.spec0, c.spec1, c.C, c.G, c.twN, c.L, c.KB,
+                             c.G ? (float)c.MN : 1.0f, nullptr, nullptr, c.br, c.yh);
+    });
+    if (rc) return rc;
+    hipError_t e = hipMemsetAsync(c.spec0, 0, c.planes * c.MN * 4, s);
+    if (e != hipSuccess) return fail(ADMM_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    const size_t sstride = c.planes * 2 * c.MN;   // one trajectory slot of s
+    for (int it = 1; it <= maxit; ++it) {
+        float2* vsave = tr.v ? tr.v + (size_t)(it - 1) * c.planes * c.N * c.L : nullptr;
+        rc = ln.run(ADMM_K_COLUMN, [&] {
+            return launch_column(c.N, vsave ? 7 : 6, c.gc, c.clds, s, c.spec0, c.spec1, c.C, c.G, c.twN, c.L, c.KB, 1.0f,
+                                 vsave, nullptr, c.br, c.yh);
+        });
+        if (rc) return rc;
+        if (it == maxit) break;
+        const Slots p = fwd_slots(it, tr.s, sstride, b0, b1);
+        if (!iso) {
+            rc = ln.run(ADMM_K_LINE, [&] {
+                return launch_line(c.L, c.Tu, c.gu, c.llds, s, c.spec1, c.spec0, p.so, p.sn, nullptr, c.twM, c.N, c.prm,
+                                   it == 1 ? 1 : 0, c.nTu, c.br);
+            });
+            if (rc) return rc;
+            continue;
+        }
+        // isotropic: s is written in place (no halo reads of s in ISO_A); with a trajectory each
+        // iteration writes its own slot and the batch norm is kept too
+        rc = ln.run(ADMM_K_LINE, [&] {
+            return launch_iso_a(c.L, c.T, dim3(c.N / c.T, (unsigned)c.ng), iso_a_lds(c.M, c.T), s, c.spec1, p.so, p.sn,
+                                c.fmap, c.qpart, c.twM, c.N, c.gplanes, c.Gp, it == 1 ? 1 : 0, c.ngb_k);
+        });
+        if (rc) return rc;
+        rc = iso_norm_step(ln, c.qpart, c.fmap, c.ngb, c.MN, c.prm, tr.nrm ? tr.nrm + (size_t)(it - 1) * c.nstride : nullptr,
+                           red, c.ny, c.prm_f);
+        if (rc) return rc;
+        rc = ln.run(ADMM_K_LINE, [&] {
+            return launch_iso_b(c.L, c.T, c.gl, iso_b_lds(c.M, c.T), s, p.sn, c.fmap, nullptr, c.spec0, c.twM, c.N, c.prm,
+                                c.bro);
+        });
+        if (rc) return rc;
+    }
+    return ln.run(ADMM_K_FINAL, [&] {
+        return launch_line_inv(c.L, c.T, c.gl, c.flds, s, c.spec1, x_out, c.twM, c.N, c.bro, c.map_out);
+    });
+}
+
 // Isotropic CU-resident solve (ADMM_PATH_RESIDENT_ISO): iteration k is one resident_iso_kernel launch (s_k, f_k ->
-// s_{k+1}, q per plane; x at the last), then the 2-pass path's norm over the planes' q (iso_r, or for a sharded
-// batch the shard sum, the caller's all-reduce and the factor) -> f_{k+1} (and |s_{k+1}| when recording).
+// s_{k+1}, q per plane; x at the last), then the 2-pass path's norm over the planes' q (iso_norm_step) -> f_{k+1}
+// (and |s_{k+1}| when recording).
 // Recording: s_{k+1} into trajectory slot k, read back from slot k - 1 -- the natural layout the 2-pass and
 // runtime-length isotropic sweeps read.  q: planes x M x N floats (a spectrum buffer, free after PREP).
-int run_resident_iso(Launcher& ln, int M, int N, size_t planes, const float* hty, float* sbuf0, float* q, float* fmap,
-                     float* x_out, const float* Ct, const float2* twM, const float2* twN, const float* prm, int maxit,
-                     const Traj& tr, const admm_batch_reducer* red) {
+int run_resident_iso(Launcher& ln, int M, int N, size_t planes, const FwdView& v, const float* hty, float* x_out,
+                     int maxit, const Traj& tr, const admm_batch_reducer* red) {
     hipStream_t s = ln.s;
     const size_t MN = (size_t)M * N, sstride = planes * 2 * MN;
-    const int nb = (int)((MN + 63) / 64);   // 64 pixels per block (group_sum)
-    const dim3 gr(nb < 2048 ? nb : 2048);
+    float* q = reinterpret_cast<float*>(v.spec1);
     for (int k = 0; k < maxit; ++k) {
-        const float* sin = tr.s && k >= 1 ? tr.s + (size_t)(k - 1) * sstride : sbuf0;
-        float* sout = tr.s ? tr.s + (size_t)k * sstride : sbuf0;
+        const float* sin = tr.s && k >= 1 ? tr.s + (size_t)(k - 1) * sstride : v.s[0];
+        float* sout = tr.s ? tr.s + (size_t)k * sstride : v.s[0];
         int rc = ln.run(ADMM_K_PLANE, [&] {
-            return admm::rs::launch_iso(M, N, planes, s, hty, sin, sout, fmap, q, x_out, Ct, twM, twN, prm, k, maxit);
+            return admm::rs::launch_iso(M, N, planes, s, hty, sin, sout, v.fmap, q, x_out, v.C, v.twM, v.twN, v.prm, k, maxit);
         });
         if (rc) return rc;
         if (k + 1 == maxit) break;
-        float* nrm_out = tr.nrm ? tr.nrm + (size_t)k * MN : nullptr;
-        if (red) {
-            rc = ln.run(ADMM_K_NORM, [&] {
-                hipLaunchKernelGGL(admm::iso_sum_kernel, gr, dim3(kThreads), 0, s, q, fmap, (int)planes, MN);
-            });
-            if (rc) return rc;
-            rc = call_reducer(red, fmap, MN, s);
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_NORM, [&] {
-                hipLaunchKernelGGL(admm::iso_fin_kernel, gr, dim3(kThreads), 0, s, fmap, MN, prm, nrm_out);
-            });
-        } else {
-            rc = ln.run(ADMM_K_NORM, [&] {
-                hipLaunchKernelGGL(admm::iso_r_kernel, gr, dim3(kThreads), 0, s, q, fmap, (int)planes, MN, prm, nrm_out);
-            });
-        }
+        rc = iso_norm_step(ln, q, v.fmap, (int)planes, MN, v.prm, tr.nrm ? tr.nrm + (size_t)k * MN : nullptr, red);
         if (rc) return rc;
     }
     return ADMM_OK;
 }
+
+// The fused isotropic solve at 256 x 256 (plane_iso.hip), the spectrum resident in the CU: per iteration one
+// plane256_iso_kernel over every plane and one iso_norm_kernel (each branch's batch norm over its own planes).
+// Recording (tslot > 0): s_{k+1} into trajectory slot k, |s_{k+1}| into norm slot k (lane-native).
+struct FusedIso {
+    void* tabs;              // lane-native tables, per branch
+    const float* prm;
+    size_t planes;
+    const plane::Branches* br;   // null: one solve
+    float4* st;              // s state, or the trajectory slots (tslot float4 apart)
+    size_t tslot;
+    float2* nrm;             // |s| slots, nslot float2 apart (null: not recorded)
+    size_t nslot;
+    float2 *fl, *ql;         // f maps; per plane q partials (forward) / R partials (reverse)
+};
+// sm: a sharded batch's sum map (this shard's sums, the caller's all-reduce of the M x N map, then f)
+int fused_iso_forward(Launcher& ln, const FusedIso& f, const float* y, float* x_out, bool psf, float2* hln, int maxit,
+                      const admm_batch_reducer* red = nullptr, float2* sm = nullptr) {
+    namespace pk = admm::plane;
+    hipStream_t s = ln.s;
+    for (int k = 0; k < maxit; ++k) {
+        int rc = ln.run(ADMM_K_PLANE, [&] {
+            return pk::launch_plane_iso(y, x_out, f.tabs, psf, hln, f.st + (k > 0 ? (size_t)(k - 1) * f.tslot : 0),
+                                        f.st + (size_t)k * f.tslot, f.fl, f.ql, f.prm, k, maxit, f.planes, s, f.br);
+        });
+        if (rc) return rc;
+        if (k + 1 == maxit) break;
+        float2* nr = f.nrm ? f.nrm + (size_t)k * f.nslot : nullptr;
+        if (!red) {
+            rc = ln.run(ADMM_K_NORM, [&] { return pk::launch_iso_norm(f.ql, f.fl, nr, f.prm, f.planes, s, f.br); });
+            if (rc) return rc;
+            continue;
+        }
+        rc = ln.run(ADMM_K_NORM, [&] { return pk::launch_iso_norm(f.ql, f.fl, nr, f.prm, f.planes, s, nullptr, sm); });
+        if (rc) return rc;
+        rc = call_reducer(red, reinterpret_cast<float*>(sm), (size_t)kMultiM * kMultiN, s);
+        if (rc) return rc;
+        rc = ln.run(ADMM_K_NORM, [&] { return pk::launch_iso_norm(f.ql, f.fl, nr, f.prm, f.planes, s, nullptr, nullptr, sm); });
+        if (rc) return rc;
+    }
+    return ADMM_OK;
+}
+
+int run_forward_generic(Launcher& ln, const float* y, float* x_out, int M, int N, size_t planes, const FwdView& v,
+                        int iso, int maxit, const Traj& tr, const admm_batch_reducer* red, int path, const Branches& br);
 
 int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t planes, const float* h, int kh,
                 int kw, const admm::ScalarSrc& sc, int iso, int maxit, unsigned char* ws, const Layout& lay,
@@ -269,17 +575,8 @@ int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t
     hipStream_t s = ln.s;
     int rc = ADMM_OK;
     const size_t MN = (size_t)M * N;
-    float2* twM = reinterpret_cast<float2*>(ws + lay.twM);
-    float2* twN = reinterpret_cast<float2*>(ws + lay.twN);
-    float* Ct = reinterpret_cast<float*>(ws + lay.C);
-    float2* Gt = kh > 0 ? reinterpret_cast<float2*>(ws + lay.G) : nullptr;
-    float* hty = kh > 0 ? reinterpret_cast<float*>(ws + lay.hty) : const_cast<float*>(y);
-    float* sbuf[2] = {reinterpret_cast<float*>(ws + lay.sA), reinterpret_cast<float*>(ws + lay.sB)};
-    float2* spec0 = reinterpret_cast<float2*>(ws + lay.spec0);
-    float2* spec1 = reinterpret_cast<float2*>(ws + lay.spec1);
+    const FwdView v = view(ws, lay, kh > 0);
     const int L = M / 2;
-    float* prm = reinterpret_cast<float*>(ws + lay.prm);   // tau = lambda / rho (ops.jl:20), rho, lambda
-    double2* SigT = tr.sig;
 
     // a grouped solve: the 2-pass / runtime-length kernels' descriptor (C / G tables tab_f apart)
     const Branches br = grp ? *grp : kOneSolve;
@@ -294,13 +591,13 @@ int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t
             int gx = grid;
             while (gx > 1 && gx > grid / 8 && (size_t)G * (gx / 2) >= 2048) gx /= 2;
             set_lds(admm::setup_grouped_kernel, lds);
-            hipLaunchKernelGGL(admm::setup_grouped_kernel, dim3(gx, (unsigned)G), dim3(kThreads), lds, s, twM, twN, Ct,
-                               Gt, h, kh, kw, M, N, sc.lam, sc.rho, br.prm_f ? G : 1, prm, br.tab_f, br.prm_f);
+            hipLaunchKernelGGL(admm::setup_grouped_kernel, dim3(gx, (unsigned)G), dim3(kThreads), lds, s, v.twM, v.twN,
+                               v.C, v.G, h, kh, kw, M, N, sc.lam, sc.rho, br.prm_f ? G : 1, v.prm, br.tab_f, br.prm_f);
             return;
         }
         set_lds(admm::setup_kernel, lds);
-        hipLaunchKernelGGL(admm::setup_kernel, dim3(grid), dim3(kThreads), lds, s, twM, twN, Ct, Gt, h, kh, kw, M,
-                           N, sc, prm, SigT);
+        hipLaunchKernelGGL(admm::setup_kernel, dim3(grid), dim3(kThreads), lds, s, v.twM, v.twN, v.C, v.G, h, kh, kw, M,
+                           N, sc, v.prm, tr.sig);
     });
     if (rc) return rc;
     if (maxit == 0) {
@@ -311,343 +608,193 @@ int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t
 
     const int path = fwd_path;
     if (generic_shape(M, N)) {   // ADMM_PATH_RESIDENT (smooth sides), _SMOOTH, _RUNTIME: the runtime-length layout
-        return run_forward_generic(ln, y, x_out, M, N, planes, kh, iso, maxit, ws, lay, tr, red, path, br);
+        return run_forward_generic(ln, y, x_out, M, N, planes, v, iso, maxit, tr, red, path, br);
     }
     if (path == ADMM_PATH_FUSED) {
         // one workgroup per plane runs all K iterations (plane_kernel.hip); lane-native H^T y in
         // spec0, lane-native s in sA -- or, recording a trajectory, s_k in its own slot of tr.s
         namespace pk = admm::plane;
-        void* ptab = ws + lay.F;
         if (tables) rc = ln.run(ADMM_K_SETUP, [&] {
-            if (grp) return pk::launch_tables_grouped(Ct, Gt, ptab, pk::grouped_count(br), br.tab_f, s);
-            return pk::launch_tables(Ct, Gt, ptab, s);
+            if (grp) return pk::launch_tables_grouped(v.C, v.G, v.F, pk::grouped_count(br), br.tab_f, s);
+            return pk::launch_tables(v.C, v.G, v.F, s);
         });
         if (rc) return rc;
         // a grouped solve: the same descriptor over the lane-native table blocks
         Branches bf = br;
         bf.tab_f = (unsigned)(pk::grouped_tables_bytes() / 4);
         rc = ln.run(ADMM_K_PLANE, [&] {
-            return pk::launch_plane(y, x_out, ptab, kh > 0, spec0, reinterpret_cast<float4*>(sbuf[0]), prm, maxit,
+            return pk::launch_plane(y, x_out, v.F, kh > 0, v.spec0, reinterpret_cast<float4*>(v.s[0]), v.prm, maxit,
                                    planes, s, tr.m ? nullptr : reinterpret_cast<float4*>(tr.s), grp ? &bf : nullptr, tr.m);
         });
         return rc;
     }
     if (path == ADMM_PATH_FUSED_ISO) {
-        // isotropic at 256 x 256: the split-iteration per-plane kernels (plane_iso.hip), the spectrum
-        // resident in the CU; per iteration one plane256_iso_kernel and one iso_norm_kernel (batch norm)
-        namespace pk = admm::plane;
-        void* ptab = ws + lay.F;
-        if (tables) rc = ln.run(ADMM_K_SETUP, [&] { return pk::launch_tables(Ct, Gt, ptab, s); });
+        // isotropic at 256 x 256: the split-iteration per-plane kernels (fused_iso_forward); q partials in spec1, a
+        // sharded batch's sum map in the plane-group partials' slot
+        if (tables) rc = ln.run(ADMM_K_SETUP, [&] { return admm::plane::launch_tables(v.C, v.G, v.F, s); });
         if (rc) return rc;
-        float2* fl = reinterpret_cast<float2*>(ws + lay.fmap);
-        float2* ql = reinterpret_cast<float2*>(spec1);
-        // recording: s_{k+1} into trajectory slot k, |s_{k+1}| into norm slot k (lane-native)
-        float4* st = reinterpret_cast<float4*>(tr.iso_lane ? tr.s : sbuf[0]);
-        const size_t tslot = tr.iso_lane ? planes * MN / 2 : 0;   // float4 per slot
-        for (int k = 0; k < maxit; ++k) {
-            rc = ln.run(ADMM_K_PLANE, [&] {
-                return pk::launch_plane_iso(y, x_out, ptab, kh > 0, spec0, st + (k > 0 ? (size_t)(k - 1) * tslot : 0),
-                                            st + (size_t)k * tslot, fl, ql, prm, k, maxit, planes, s);
-            });
-            if (rc) return rc;
-            if (k + 1 < maxit) {
-                float2* nr = tr.iso_lane ? reinterpret_cast<float2*>(tr.nrm + (size_t)k * MN) : nullptr;
-                if (red) {
-                    // sharded batch: this shard's sums, the caller's all-reduce of the M x N map, then f
-                    float2* sm = reinterpret_cast<float2*>(ws + lay.part);
-                    rc = ln.run(ADMM_K_NORM, [&] { return pk::launch_iso_norm(ql, fl, nr, prm, planes, s, nullptr, sm); });
-                    if (rc) return rc;
-                    rc = call_reducer(red, reinterpret_cast<float*>(sm), MN, s);
-                    if (rc) return rc;
-                    rc = ln.run(ADMM_K_NORM, [&] {
-                        return pk::launch_iso_norm(ql, fl, nr, prm, planes, s, nullptr, nullptr, sm);
-                    });
-                } else {
-                    rc = ln.run(ADMM_K_NORM, [&] { return pk::launch_iso_norm(ql, fl, nr, prm, planes, s); });
-                }
-                if (rc) return rc;
-            }
-        }
-        return ADMM_OK;
+        const size_t kE = MN / 2;   // lane-native float2 elements per plane
+        const FusedIso f{v.F, v.prm, planes, nullptr, reinterpret_cast<float4*>(tr.iso_lane ? tr.s : v.s[0]),
+                         tr.iso_lane ? planes * kE : 0, tr.iso_lane ? reinterpret_cast<float2*>(tr.nrm) : nullptr, kE,
+                         reinterpret_cast<float2*>(v.fmap), v.spec1};
+        return fused_iso_forward(ln, f, y, x_out, kh > 0, v.spec0, maxit, red, reinterpret_cast<float2*>(v.part));
     }
-    const int T = line_T(M, N);
-    const int KB = column_KB(M, N);
-    // the per-iteration line update runs 4-line blocks at 512-point lines (its just-in-time loads let 4 of
-    // them share a CU, admm_kernels.hip line_kernel); the one-off line transforms keep T
-    // 512-point lines: 8-line update blocks of 512 threads (round 5, tools/c4_line_sweep.sh: line pass 1.217 ->
-    // 1.196 ms at c4; 4 lines x 256 threads was round 1's choice; 16 x 1024, 4 x 512 and 8 x 1024 slower:
-    // profiles/r05_c4_line_sweep.jsonl)
-    const int Tu = (M == 512 && T > 4) ? 8 : T;
-    const int nTu = (M == 512 && Tu == 8) ? 512 : kThreads;
-    const size_t llds = line_lds(M, Tu), flds = fwdinv_lds(M, T), clds = column_lds(N, KB);
-    float* fmap = iso ? reinterpret_cast<float*>(ws + lay.fmap) : nullptr;
-    float* part = iso ? reinterpret_cast<float*>(ws + lay.part) : nullptr;
-    const size_t np = planes;
-    const dim3 gl(N / T, (unsigned)np), gc(L / KB, (unsigned)np);
+    const TwoPass c = two_pass_single(ln, M, N, planes, line_T(M, N), v, br);
     if (path == ADMM_PATH_RESIDENT || path == ADMM_PATH_RESIDENT_ISO) {
         // power-of-two sides admm_resident.hip compiled: one workgroup per plane runs all K iterations (s_k into
         // the trajectory slots when recording, natural layout, as the 2-pass sweep reads them); H^T y from the
-        // 2-pass PREP kernels (line, column x conj(Sigma_c), line), the first line spectrum formed in the kernel
+        // 2-pass kernels (line, column x conj(Sigma_c), line), the first line spectrum formed in the kernel
+        float* hty = kh > 0 ? v.hty : const_cast<float*>(y);
         if (kh > 0) {
-            rc = ln.run(ADMM_K_PREP, [&] { return launch_line_fwd(L, T, gl, flds, s, y, spec0, twM, N); });
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_PREP, [&] { return launch_column(N, 1, gc, clds, s, spec0, spec1, Ct, Gt, twN, L, KB, 1.0f); });
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_PREP, [&] { return launch_line_inv(L, T, gl, flds, s, spec1, hty, twM, N); });
+            rc = two_pass_conv(c, ADMM_K_PREP, 1, y, hty);
             if (rc) return rc;
         }
-        if (path == ADMM_PATH_RESIDENT_ISO)
-            return run_resident_iso(ln, M, N, planes, hty, sbuf[0], reinterpret_cast<float*>(spec1), fmap, x_out, Ct, twM,
-                                    twN, prm, maxit, tr, red);
+        if (path == ADMM_PATH_RESIDENT_ISO) return run_resident_iso(ln, M, N, planes, v, hty, x_out, maxit, tr, red);
         return ln.run(ADMM_K_PLANE, [&] {
-            return admm::rs::launch(M, N, planes, s, hty, sbuf[0], sbuf[1], tr.s, np * 2 * MN, x_out, Ct, twM, twN, prm,
-                                    maxit);
+            return admm::rs::launch(M, N, planes, s, hty, v.s[0], v.s[1], tr.s, planes * 2 * MN, x_out, v.C, v.twM, v.twN,
+                                    v.prm, maxit);
         });
     }
-    // PREP: Y_h = F(H^T y) = conj(Sigma_c) F y as a 2-D packed spectrum straight from F y (line transform, column
-    // transform x conj(Sigma_c)), never H^T y in space: every iteration adds it to the spectrum of rho D^T w in
-    // the column pass, so the per-iteration fp32 transforms carry only rho D^T w (x 16x, y_bar / h_bar ~2-9x closer
-    // to the fp64 oracle than with H^T y added before the line transform; DESIGN.md s1 "H^T y in the spectrum").
-    // Iteration 1 (w = 0) transforms a zero line spectrum and adds Y_h.
-    float2* yh = reinterpret_cast<float2*>(ws + lay.hty);   // the workspace's H^T y slot holds Y_h on this path
-    rc = ln.run(ADMM_K_PREP, [&] { return launch_line_fwd(L, T, gl, flds, s, y, spec0, twM, N); });
-    if (rc) return rc;
-    rc = ln.run(ADMM_K_PREP, [&] {
-        return launch_column(N, 5, gc, clds, s, spec0, spec1, Ct, kh > 0 ? Gt : nullptr, twN, L, KB,
-                             kh > 0 ? (float)MN : 1.0f, nullptr, nullptr, br, yh);
-    });
-    if (rc) return rc;
-    {
-        hipError_t e = hipMemsetAsync(spec0, 0, np * MN * 4, s);
-        if (e != hipSuccess) return fail(ADMM_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-    }
-    const size_t sstride = np * 2 * MN;   // one trajectory slot of s
-    for (int it = 1; it <= maxit; ++it) {
-        float2* vsave = tr.v ? tr.v + (size_t)(it - 1) * np * N * L : nullptr;
-        rc = ln.run(ADMM_K_COLUMN, [&] {
-            return launch_column(N, vsave ? 7 : 6, gc, clds, s, spec0, spec1, Ct, Gt, twN, L, KB, 1.0f, vsave, nullptr,
-                                 br, yh);
-        });
-        if (rc) return rc;
-        if (it < maxit && !iso) {
-            float* so;
-            float* sn;
-            if (tr.s) {
-                so = it >= 2 ? tr.s + (size_t)(it - 2) * sstride : sbuf[0];
-                sn = tr.s + (size_t)(it - 1) * sstride;
-            } else {
-                so = (it & 1) ? sbuf[1] : sbuf[0];   // iteration 1 reads nothing (s_zero)
-                sn = (it & 1) ? sbuf[0] : sbuf[1];
-            }
-            rc = ln.run(ADMM_K_LINE, [&] {
-                return launch_line(L, Tu, dim3(N / Tu, (unsigned)np), llds, s, spec1, spec0, so, sn, nullptr, twM, N, prm,
-                            it == 1 ? 1 : 0, nTu, br);
-            });
-        } else if (it < maxit) {
-            // isotropic: s is written in place (no halo reads of s in ISO_A); with a trajectory each
-            // iteration writes its own slot and the batch norm is kept too
-            float* so = sbuf[0];
-            float* sn = sbuf[0];
-            if (tr.s) {
-                so = it >= 2 ? tr.s + (size_t)(it - 2) * sstride : sbuf[0];
-                sn = tr.s + (size_t)(it - 1) * sstride;
-            }
-            float* nrm_out = tr.nrm ? tr.nrm + (size_t)(it - 1) * MN : nullptr;
-            const int ng = iso_ngroups(np);
-            rc = ln.run(ADMM_K_LINE, [&] {
-                return launch_iso_a(L, T, dim3(N / T, ng), iso_a_lds(M, T), s, spec1, so, sn, fmap, part, twM, N, (int)np,
-                             iso_group(np), it == 1 ? 1 : 0);
-            });
-            if (rc) return rc;
-            const int nb = (int)((MN + 63) / 64);   // 64 pixels per block (group_sum)
-            const dim3 gr(nb < 2048 ? nb : 2048);
-            if (red) {
-                // sharded batch: per-shard sum -> caller's all-reduce -> BT factor
-                rc = ln.run(ADMM_K_NORM, [&] {
-                    hipLaunchKernelGGL(admm::iso_sum_kernel, gr, dim3(kThreads), 0, s, part, fmap, ng, MN);
-                });
-                if (rc) return rc;
-                rc = call_reducer(red, fmap, MN, s);
-                if (rc) return rc;
-                rc = ln.run(ADMM_K_NORM, [&] {
-                    hipLaunchKernelGGL(admm::iso_fin_kernel, gr, dim3(kThreads), 0, s, fmap, MN, prm, nrm_out);
-                });
-            } else {
-                rc = ln.run(ADMM_K_NORM, [&] {
-                    hipLaunchKernelGGL(admm::iso_r_kernel, gr, dim3(kThreads), 0, s, part, fmap, ng, MN, prm, nrm_out);
-                });
-            }
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_LINE, [&] {
-                return launch_iso_b(L, T, gl, iso_b_lds(M, T), s, sn, fmap, nullptr, spec0, twM, N, prm);
-            });
-        } else {
-            rc = ln.run(ADMM_K_FINAL, [&] { return launch_line_inv(L, T, gl, flds, s, spec1, x_out, twM, N); });
-        }
-        if (rc) return rc;
-    }
-    return ADMM_OK;
+    return two_pass_forward(c, y, x_out, maxit, iso != 0, tr, v.s[0], iso ? v.s[0] : v.s[1], red);
 }
 
-int run_forward_generic(Launcher& ln, const float* y, float* x_out, int M, int N, size_t planes, int kh,
-                        int iso, int maxit, unsigned char* ws, const Layout& lay,
-                        const Traj& tr, const admm_batch_reducer* red, int path, const Branches& br) {
+// ---- the runtime-length kernels (admm_generic.hip, admm_generic_bwd.hip) -----------------------------------
+struct GenPass {
+    int M, N, H, T, KB;
+    size_t planes;
+    admm::gen::FPlan pM, pN;
+    dim3 gl, gc;
+    size_t lfw, lup, lcol;   // LDS: line_fwd / line_inv; line_upd / iso_b and the adjoints; column
+    // compile-time-plan kernels where this build has the length (admm_smooth.hip): the column pass needs
+    // N, the line passes M (forward only)
+    bool smc, sml;
+};
+GenPass gen_pass(int M, int N, size_t planes, bool smooth) {
+    namespace g = admm::gen;
+    GenPass p{M, N, M / 2 + 1, gen_T(M, N), gen_KB(M, N), planes, make_fplan(M), make_fplan(N)};
+    p.gl = dim3(gen_nb(N, p.T), (unsigned)planes);
+    p.gc = dim3((p.H + p.KB - 1) / p.KB, (unsigned)planes);
+    p.lfw = gen_lds_line(M, p.T, false);
+    p.lup = gen_lds_line(M, p.T, true);
+    p.lcol = gen_lds_col(N, p.KB);
+    set_lds(g::line_fwd_kernel, p.lfw);
+    set_lds(g::line_inv_kernel, p.lfw);
+    set_lds(g::column_kernel, p.lcol);
+    p.smc = smooth && admm::sm::has_length(N);
+    p.sml = smooth && admm::sm::has_length(M);
+    return p;
+}
+
+int gen_line_fwd(Launcher& ln, const GenPass& p, const FwdView& v, int cls, const float* src, float2* dst) {
+    return ln.run(cls, [&] {
+        if (p.sml) return admm::sm::launch_line_fwd(p.M, p.N, p.planes, ln.s, src, dst, v.twM);
+        hipLaunchKernelGGL(admm::gen::line_fwd_kernel, p.gl, dim3(256), p.lfw, ln.s, src, dst, v.twM, p.pM, p.N, p.T);
+        return 0;
+    });
+}
+
+int gen_line_inv(Launcher& ln, const GenPass& p, const FwdView& v, int cls, const float2* src, float* dst) {
+    return ln.run(cls, [&] {
+        if (p.sml) return admm::sm::launch_line_inv(p.M, p.N, p.planes, ln.s, src, dst, v.twM);
+        hipLaunchKernelGGL(admm::gen::line_inv_kernel, p.gl, dim3(256), p.lfw, ln.s, src, dst, v.twM, p.pM, p.N, p.T);
+        return 0;
+    });
+}
+
+// dst = F^-1 [multiplier] F src with the runtime-length kernels (mode 1: conj(Sigma_c), H^T; 2: Sigma_c, H)
+int gen_conv(Launcher& ln, const GenPass& p, const FwdView& v, int cls, int mode, const float* src, float* dst) {
+    int rc = gen_line_fwd(ln, p, v, cls, src, v.spec0);
+    if (rc) return rc;
+    rc = ln.run(cls, [&] {
+        if (p.smc)
+            return admm::sm::launch_column(p.M, p.N, p.planes, ln.s, v.spec0, v.spec1, v.C, v.G, v.twN, 1.0f, mode,
+                                           opt(ADMM_OPT_SMOOTH));
+        hipLaunchKernelGGL(admm::gen::column_kernel, p.gc, dim3(256), p.lcol, ln.s, v.spec0, v.spec1, v.C, v.G, v.twN, p.pN,
+                           p.H, p.KB, mode, 1.0f);
+        return 0;
+    });
+    if (rc) return rc;
+    return gen_line_inv(ln, p, v, cls, v.spec1, dst);
+}
+
+int run_forward_generic(Launcher& ln, const float* y, float* x_out, int M, int N, size_t planes, const FwdView& v,
+                        int iso, int maxit, const Traj& tr, const admm_batch_reducer* red, int path, const Branches& br) {
     namespace g = admm::gen;
     hipStream_t s = ln.s;
     int rc = ADMM_OK;
     const size_t MN = (size_t)M * N;
-    const int H = M / 2 + 1;
-    const float2* twM = reinterpret_cast<float2*>(ws + lay.twM);
-    const float2* twN = reinterpret_cast<float2*>(ws + lay.twN);
-    const float* Ct = reinterpret_cast<float*>(ws + lay.C);
-    const float2* Gt = kh > 0 ? reinterpret_cast<float2*>(ws + lay.G) : nullptr;
-    const float* hty = kh > 0 ? reinterpret_cast<float*>(ws + lay.hty) : y;
-    float* sbuf[2] = {reinterpret_cast<float*>(ws + lay.sA), reinterpret_cast<float*>(ws + lay.sB)};
-    float2* spec0 = reinterpret_cast<float2*>(ws + lay.spec0);
-    float2* spec1 = reinterpret_cast<float2*>(ws + lay.spec1);
-    float* xg = reinterpret_cast<float*>(ws + lay.xg);
-    float* fmap = iso ? reinterpret_cast<float*>(ws + lay.fmap) : nullptr;
-    float* part = iso ? reinterpret_cast<float*>(ws + lay.part) : nullptr;
-    const float* prm = reinterpret_cast<const float*>(ws + lay.prm);
-    const g::FPlan pM = make_fplan(M), pN = make_fplan(N);
-    const int T = gen_T(M, N), KB = gen_KB(M, N);
-    const dim3 gl(gen_nb(N, T), (unsigned)planes), gc((H + KB - 1) / KB, (unsigned)planes);
-    const size_t lfw = gen_lds_line(M, T, false);                    // line_fwd / line_inv
-    const size_t lup = gen_lds_line(M, T, true);                     // line_upd / iso_b
-    const size_t lcol = gen_lds_col(N, KB);
-    set_lds(g::line_fwd_kernel, lfw);
-    set_lds(g::line_inv_kernel, lfw);
-    set_lds(g::line_upd_kernel, lup);
-    set_lds(g::iso_b_kernel, lup);
-    set_lds(g::column_kernel, lcol);
-    // compile-time-plan kernels where this build has the length (admm_smooth.hip): the column pass needs
-    // N, the line passes M
     // (a grouped solve runs the runtime-length kernels only: they take the group offsets)
-    const bool smooth = opt(ADMM_OPT_SMOOTH) != 0 && br.nbr != 0;
-    const bool smc = smooth && admm::sm::has_length(N);
-    const bool sml = smooth && admm::sm::has_length(M);
-    auto line_fwd = [&](const float* src, float2* dst) {
-        return ln.run(ADMM_K_PREP, [&] {
-            if (sml) return admm::sm::launch_line_fwd(M, N, planes, s, src, dst, twM);
-            hipLaunchKernelGGL(g::line_fwd_kernel, gl, dim3(256), lfw, s, src, dst, twM, pM, N, T);
-            return 0;
-        });
-    };
+    const GenPass p = gen_pass(M, N, planes, opt(ADMM_OPT_SMOOTH) != 0 && br.nbr != 0);
+    set_lds(g::line_upd_kernel, p.lup);
+    set_lds(g::iso_b_kernel, p.lup);
+    const size_t sstride = planes * 2 * MN;   // one trajectory slot of s
     // CU-resident solve (admm_resident.hip): anisotropic, no dim-2 spectra or isotropic norms recorded; it
-    // forms the first line spectrum itself, so PREP only produces H^T y
-    const bool res = path == ADMM_PATH_RESIDENT || path == ADMM_PATH_RESIDENT_ISO;   // plan_paths
+    // forms the first line spectrum itself, so PREP only produces H^T y in space (with a PSF: F^-1 conj(Sigma_c) F y,
+    // ops.jl:71-81)
+    if (path == ADMM_PATH_RESIDENT || path == ADMM_PATH_RESIDENT_ISO) {   // plan_paths
+        const float* hty = v.G ? v.hty : y;
+        if (v.G) {
+            rc = gen_conv(ln, p, v, ADMM_K_PREP, 1, y, v.hty);
+            if (rc) return rc;
+        }
+        if (path == ADMM_PATH_RESIDENT_ISO) return run_resident_iso(ln, M, N, planes, v, hty, x_out, maxit, tr, red);
+        return ln.run(ADMM_K_PLANE, [&] {
+            return admm::rs::launch(M, N, planes, s, hty, v.s[0], v.s[1], tr.s, sstride, x_out, v.C, v.twM, v.twN, v.prm, maxit);
+        });
+    }
     // the 2-pass kernels take H^T y in the spectral domain: Y_h = conj(Sigma_c) F y (with a PSF) stored once as the
     // column pass's 2-D spectrum and added to every iteration's spectrum of rho D^T w
-    float2* yh = reinterpret_cast<float2*>(ws + lay.hty);
-    if (!res) {
-        rc = line_fwd(y, spec0);
-        if (rc) return rc;
-        rc = ln.run(ADMM_K_PREP, [&] {
-            hipLaunchKernelGGL(g::column_kernel, gc, dim3(256), lcol, s, spec0, spec1, Ct, Gt, twN, pN, H, KB, 32 | 1,
-                               kh > 0 ? (float)MN : 1.0f, (float2*)nullptr, (double*)nullptr, yh, br);
-            return 0;
-        });
-        if (rc) return rc;
-        hipError_t e = hipMemsetAsync(spec0, 0, planes * (size_t)H * N * 8, s);   // iteration 1: w = 0
-        if (e != hipSuccess) return fail(ADMM_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-    }
-    // PREP of the resident solves: H^T y in space (with a PSF: F^-1 conj(Sigma_c) F y, ops.jl:71-81)
-    if (res && kh > 0) {
-        rc = line_fwd(y, spec0);
-        if (rc) return rc;
-    }
-    if (res && kh > 0) {
-        rc = ln.run(ADMM_K_PREP, [&] {
-            if (smc) return admm::sm::launch_column(M, N, planes, s, spec0, spec1, Ct, Gt, twN, 1.0f, 1, opt(ADMM_OPT_SMOOTH));
-            hipLaunchKernelGGL(g::column_kernel, gc, dim3(256), lcol, s, spec0, spec1, Ct, Gt, twN, pN, H, KB, 1, 1.0f);
-            return 0;
-        });
-        if (rc) return rc;
-        rc = ln.run(ADMM_K_PREP, [&] {
-            if (sml) return admm::sm::launch_line_inv(M, N, planes, s, spec1, const_cast<float*>(hty), twM);
-            hipLaunchKernelGGL(g::line_inv_kernel, gl, dim3(256), lfw, s, spec1, const_cast<float*>(hty), twM, pM, N, T);
-            return 0;
-        });
-        if (rc) return rc;
-    }
+    float2* yh = v.yh();
+    rc = gen_line_fwd(ln, p, v, ADMM_K_PREP, y, v.spec0);
+    if (rc) return rc;
+    rc = ln.run(ADMM_K_PREP, [&] {
+        hipLaunchKernelGGL(g::column_kernel, p.gc, dim3(256), p.lcol, s, v.spec0, v.spec1, v.C, v.G, v.twN, p.pN, p.H, p.KB,
+                           32 | 1, v.G ? (float)MN : 1.0f, (float2*)nullptr, (double*)nullptr, yh, br);
+        return 0;
+    });
+    if (rc) return rc;
+    hipError_t e = hipMemsetAsync(v.spec0, 0, planes * (size_t)p.H * N * 8, s);   // iteration 1: w = 0
+    if (e != hipSuccess) return fail(ADMM_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     const int ng = iso_ngroups(planes);
-    const size_t sstride = planes * 2 * MN;   // one trajectory slot of s
-    if (path == ADMM_PATH_RESIDENT_ISO)
-        return run_resident_iso(ln, M, N, planes, hty, sbuf[0], reinterpret_cast<float*>(spec1), fmap, x_out, Ct, twM, twN,
-                                prm, maxit, tr, red);
-    if (res) {
-        return ln.run(ADMM_K_PLANE, [&] {
-            return admm::rs::launch(M, N, planes, s, hty, sbuf[0], sbuf[1], tr.s, sstride, x_out, Ct, twM, twN, prm, maxit);
-        });
-    }
     for (int it = 1; it <= maxit; ++it) {
         // trajectory for h_bar: the dim-2 spectrum of iteration it before the multiply
-        float2* vsave = tr.v ? tr.v + (size_t)(it - 1) * planes * N * H : nullptr;
+        float2* vsave = tr.v ? tr.v + (size_t)(it - 1) * planes * N * p.H : nullptr;
         rc = ln.run(ADMM_K_COLUMN, [&] {
-            if (smc && !vsave)
-                return admm::sm::launch_column(M, N, planes, s, spec0, spec1, Ct, Gt, twN, 1.0f, 0, opt(ADMM_OPT_SMOOTH), yh);
-            hipLaunchKernelGGL(g::column_kernel, gc, dim3(256), lcol, s, spec0, spec1, Ct, Gt, twN, pN, H, KB,
-                               (vsave ? 4 : 0) | 16, 1.0f, vsave, (double*)nullptr, yh, br);
+            if (p.smc && !vsave)
+                return admm::sm::launch_column(M, N, planes, s, v.spec0, v.spec1, v.C, v.G, v.twN, 1.0f, 0,
+                                               opt(ADMM_OPT_SMOOTH), yh);
+            hipLaunchKernelGGL(g::column_kernel, p.gc, dim3(256), p.lcol, s, v.spec0, v.spec1, v.C, v.G, v.twN, p.pN, p.H,
+                               p.KB, (vsave ? 4 : 0) | 16, 1.0f, vsave, (double*)nullptr, yh, br);
             return 0;
         });
         if (rc) return rc;
         const bool last = it == maxit;
-        rc = ln.run(last ? ADMM_K_FINAL : ADMM_K_LINE, [&] {
-            if (sml) return admm::sm::launch_line_inv(M, N, planes, s, spec1, last ? x_out : xg, twM);
-            hipLaunchKernelGGL(g::line_inv_kernel, gl, dim3(256), lfw, s, spec1, last ? x_out : xg, twM, pM, N, T);
-            return 0;
-        });
+        rc = gen_line_inv(ln, p, v, last ? ADMM_K_FINAL : ADMM_K_LINE, v.spec1, last ? x_out : v.xg);
         if (rc) return rc;
         if (last) break;
+        const Slots sl = fwd_slots(it, tr.s, sstride, v.s[0], iso ? v.s[0] : v.s[1]);
         if (!iso) {
-            float* so = (it & 1) ? sbuf[1] : sbuf[0];   // iteration 1 reads nothing (first)
-            float* sn = (it & 1) ? sbuf[0] : sbuf[1];
-            if (tr.s) {   // s_it into its own trajectory slot
-                so = it >= 2 ? tr.s + (size_t)(it - 2) * sstride : sbuf[0];
-                sn = tr.s + (size_t)(it - 1) * sstride;
-            }
             rc = ln.run(ADMM_K_LINE, [&] {
-                if (sml) return admm::sm::launch_line_upd(M, N, planes, s, xg, so, sn, nullptr, spec0, twM, prm, it == 1 ? 1 : 0);
-                hipLaunchKernelGGL(g::line_upd_kernel, gl, dim3(256), lup, s, xg, so, sn, (const float*)nullptr, spec0, twM,
-                                   pM, N, T, prm, it == 1 ? 1 : 0, br);
+                if (p.sml)
+                    return admm::sm::launch_line_upd(M, N, planes, s, v.xg, sl.so, sl.sn, nullptr, v.spec0, v.twM, v.prm,
+                                                     it == 1 ? 1 : 0);
+                hipLaunchKernelGGL(g::line_upd_kernel, p.gl, dim3(256), p.lup, s, v.xg, sl.so, sl.sn, (const float*)nullptr,
+                                   v.spec0, v.twM, p.pM, N, p.T, v.prm, it == 1 ? 1 : 0, br);
                 return 0;
             });
             if (rc) return rc;
             continue;
         }
-        float* sa = sbuf[0];
-        const float* s_in = sbuf[0];
-        if (tr.s) {
-            s_in = it >= 2 ? tr.s + (size_t)(it - 2) * sstride : sbuf[0];
-            sa = tr.s + (size_t)(it - 1) * sstride;
-        }
-        float* nrm_out = tr.nrm ? tr.nrm + (size_t)(it - 1) * MN : nullptr;
         rc = ln.run(ADMM_K_LINE, [&] {
-            hipLaunchKernelGGL(g::iso_a_kernel, dim3(gen_nb(N, T), ng), dim3(256), (size_t)T * M * 4, s, xg, s_in, sa, fmap,
-                               part, M, N, (int)planes, iso_group(planes), T, it == 1 ? 1 : 0);
+            hipLaunchKernelGGL(g::iso_a_kernel, dim3(gen_nb(N, p.T), ng), dim3(256), (size_t)p.T * M * 4, s, v.xg, sl.so,
+                               sl.sn, v.fmap, v.part, M, N, (int)planes, iso_group(planes), p.T, it == 1 ? 1 : 0);
         });
         if (rc) return rc;
-        const int nb = (int)((MN + 63) / 64);   // 64 pixels per block (group_sum)
-        const dim3 gr(nb < 2048 ? nb : 2048);
-        if (red) {
-            rc = ln.run(ADMM_K_NORM, [&] {
-                hipLaunchKernelGGL(admm::iso_sum_kernel, gr, dim3(kThreads), 0, s, part, fmap, ng, MN);
-            });
-            if (rc) return rc;
-            rc = call_reducer(red, fmap, MN, s);
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_NORM, [&] {
-                hipLaunchKernelGGL(admm::iso_fin_kernel, gr, dim3(kThreads), 0, s, fmap, MN, prm, nrm_out);
-            });
-        } else {
-            rc = ln.run(ADMM_K_NORM, [&] {
-                hipLaunchKernelGGL(admm::iso_r_kernel, gr, dim3(kThreads), 0, s, part, fmap, ng, MN, prm, nrm_out);
-            });
-        }
+        rc = iso_norm_step(ln, v.part, v.fmap, ng, MN, v.prm, tr.nrm ? tr.nrm + (size_t)(it - 1) * MN : nullptr, red);
         if (rc) return rc;
         rc = ln.run(ADMM_K_LINE, [&] {
-            hipLaunchKernelGGL(g::iso_b_kernel, gl, dim3(256), lup, s, sa, fmap, (const float*)nullptr, spec0, twM, pM, N, T,
-                               prm);
+            hipLaunchKernelGGL(g::iso_b_kernel, p.gl, dim3(256), p.lup, s, sl.sn, v.fmap, (const float*)nullptr, v.spec0,
+                               v.twM, p.pM, N, p.T, v.prm);
         });
         if (rc) return rc;
     }
@@ -730,34 +877,275 @@ int launch_iso_adj_b(int L, int T, dim3 g, size_t lds, hipStream_t s, const floa
     return -1;
 }
 
+// ---- reverse sweeps -------------------------------------------------------------------------------------------
+// Step k = K .. 1 reads s_{k-1} (sk1) and, for rho_bar, s_k (skk) from the trajectory, |s_{k-1}| (isotropic),
+// sbar_{k+1} from one sbar buffer (none at k = K) and writes sbar_k to the other; its (rho_bar, tau_bar) partial
+// rows start at row (K - k) x rows.
+struct RevStep {
+    const float *sk1, *skk, *nrm1, *sbi;
+    float* sbo;
+    double* rp;
+};
+RevStep rev_step(int k, int K, const SweepBufs& b, size_t sstride, size_t nstride, int rows) {
+    return RevStep{k >= 2 ? b.traj + (size_t)(k - 2) * sstride : nullptr,
+                   k < K ? b.traj + (size_t)(k - 1) * sstride : nullptr,
+                   b.nrm && k >= 2 ? b.nrm + (size_t)(k - 2) * nstride : nullptr,
+                   k < K ? b.sb[k & 1] : nullptr,
+                   b.sb[(k & 1) ^ 1],
+                   b.part + (size_t)(K - k) * rows * 2};
+}
+
+// The 2-pass reverse sweep: the line transform of x_bar, then per step the column pass (with h_bar: the recorded
+// spectrum of the step and the Q accumulators) and the line adjoint -- or, isotropic, ISO_ADJ_A (plane groups) ->
+// ISO_ADJ_R (batch R map, tau_bar) -> ISO_ADJ_B (per plane); k = 1 launches no ISO_ADJ_R or _B.
+// ln_traj: the trajectory is in the fused kernel's lane-native layout (M = 256, anisotropic)
+int two_pass_reverse(const TwoPass& c, const SweepBufs& b, const float* x_bar, int K, bool iso, bool ln_traj,
+                     const admm_batch_reducer* red = nullptr) {
+    Launcher& ln = c.ln;
+    hipStream_t s = ln.s;
+    const size_t sstride = c.planes * 2 * c.MN;
+    const size_t alds = line_lds(c.M, c.T) + 8 * 16;
+    int rc = ln.run(ADMM_K_PREP, [&] {
+        return launch_line_fwd(c.L, c.T, c.gl, c.flds, s, x_bar, c.spec0, c.twM, c.N, c.bro, c.map_out);
+    });
+    if (rc) return rc;
+    for (int k = K; k >= 1; --k) {
+        float2* vs = b.v ? b.v + (size_t)(k - 1) * c.planes * c.N * c.L : nullptr;
+        rc = ln.run(ADMM_K_COLUMN, [&] {
+            return launch_column(c.N, b.v ? 4 : 0, c.gc, c.clds, s, c.spec0, c.spec1, c.C, c.G, c.twN, c.L, c.KB, 1.0f, vs,
+                                 b.Qp, c.bro);
+        });
+        if (rc) return rc;
+        const RevStep r = rev_step(k, K, b, sstride, c.nstride, c.rows);
+        const float* skk = b.xK ? r.skk : nullptr;   // s_k and D x_K enter rho_bar's <D vbar, D x_k> only
+        if (!iso) {
+            rc = ln.run(ADMM_K_ADJ, [&] {
+                return launch_line_adj(c.L, c.T, c.gl, alds, s, c.spec1, r.sk1, skk, b.xK, r.sbi, r.sbo, b.vsum, c.spec0,
+                                       r.rp, c.twM, c.N, c.prm, k == 1 ? 1 : 0, k == K ? 1 : 0, ln_traj, c.bro, c.pbs);
+            });
+            if (rc) return rc;
+            continue;
+        }
+        rc = ln.run(ADMM_K_ADJ, [&] {
+            return launch_iso_adj_a(c.L, c.T, dim3(c.N / c.T, (unsigned)c.ng), iso_a_lds(c.M, c.T) + 8 * 16, s, c.spec1,
+                                    r.sk1, skk, b.xK, r.nrm1, r.sbi, b.wbar, b.vsum, b.Rpart, r.rp, c.twM, c.N, c.gplanes,
+                                    c.Gp, c.prm, k == 1 ? 1 : 0, k == K ? 1 : 0, c.bro, c.ngb_k, c.pbs);
+        });
+        if (rc) return rc;
+        if (k == 1) break;
+        rc = ln.run(ADMM_K_NORM, [&] {
+            hipLaunchKernelGGL(admm::iso_adj_r_kernel, dim3(kIsoAdjRBlocks, c.ny), dim3(kThreads), 0, s, b.Rpart, b.Rmap,
+                               r.nrm1, c.ngb, c.MN, c.prm, r.rp + (size_t)c.r_off * 2, c.prm_f, c.pbs);
+        });
+        if (rc) return rc;
+        // sharded batch: tau_bar above used this shard's R (shard contributions add up, like every other
+        // parameter gradient); sbar needs the whole batch's R
+        if (red) {
+            rc = call_reducer(red, b.Rmap, c.MN, s);
+            if (rc) return rc;
+        }
+        rc = ln.run(ADMM_K_ADJ, [&] {
+            return launch_iso_adj_b(c.L, c.T, c.gl, iso_b_lds(c.M, c.T), s, b.wbar, r.sbi, r.sk1, r.nrm1, b.Rmap, r.sbo,
+                                    c.spec0, c.twM, c.N, c.prm, c.bro);
+        });
+        if (rc) return rc;
+    }
+    return ADMM_OK;
+}
+
+// The runtime-length reverse sweep (admm_generic_bwd.hip): per step column, line inverse -> vbar_k in HBM (the
+// forward's x slot), then the line adjoint (aniso) or ISO_ADJ_A -> ISO_ADJ_R -> ISO_ADJ_B.  These kernels take s_k and
+// x_K (rho_bar's terms) whether or not rho_bar is wanted.
+int runtime_reverse(Launcher& ln, const GenPass& p, const FwdView& v, const SweepBufs& b, const float* x_bar,
+                    const float* xK, int K, bool iso, int rows, int r_off, const admm_batch_reducer* red) {
+    namespace g = admm::gen;
+    hipStream_t s = ln.s;
+    const int M = p.M, N = p.N;
+    const size_t MN = (size_t)M * N, sstride = p.planes * 2 * MN;
+    const int ngi = iso_ngroups(p.planes);
+    set_lds(g::line_adj_kernel, p.lup);
+    set_lds(g::iso_adj_b_kernel, p.lup);
+    float* vb = v.xg;
+    int rc = gen_line_fwd(ln, p, v, ADMM_K_PREP, x_bar, v.spec0);
+    if (rc) return rc;
+    for (int k = K; k >= 1; --k) {
+        float2* vs = b.v ? b.v + (size_t)(k - 1) * p.planes * N * p.H : nullptr;
+        rc = ln.run(ADMM_K_COLUMN, [&] {
+            hipLaunchKernelGGL(g::column_kernel, p.gc, dim3(256), p.lcol, s, v.spec0, v.spec1, v.C, v.G, v.twN, p.pN, p.H,
+                               p.KB, b.v ? 8 : 0, 1.0f, vs, b.Qp);
+        });
+        if (rc) return rc;
+        rc = gen_line_inv(ln, p, v, ADMM_K_LINE, v.spec1, vb);
+        if (rc) return rc;
+        const RevStep r = rev_step(k, K, b, sstride, MN, rows);
+        if (!iso) {
+            rc = ln.run(ADMM_K_ADJ, [&] {
+                hipLaunchKernelGGL(g::line_adj_kernel, p.gl, dim3(256), p.lup, s, vb, r.sk1, r.skk, xK, r.sbi, r.sbo,
+                                   b.vsum, v.spec0, r.rp, v.twM, p.pM, N, p.T, v.prm);
+            });
+            if (rc) return rc;
+            continue;
+        }
+        rc = ln.run(ADMM_K_ADJ, [&] {
+            hipLaunchKernelGGL(g::iso_adj_a_kernel, dim3(gen_nb(N, p.T), (unsigned)ngi), dim3(256), (size_t)p.T * M * 4, s,
+                               vb, r.sk1, r.skk, xK, r.nrm1, r.sbi, b.wbar, b.vsum, b.Rpart, r.rp, M, N, (int)p.planes,
+                               iso_group(p.planes), p.T, v.prm);
+        });
+        if (rc) return rc;
+        if (k == 1) break;
+        rc = ln.run(ADMM_K_NORM, [&] {
+            hipLaunchKernelGGL(admm::iso_adj_r_kernel, dim3(kIsoAdjRBlocks), dim3(kThreads), 0, s, b.Rpart, b.Rmap, r.nrm1,
+                               ngi, MN, v.prm, r.rp + (size_t)r_off * 2);
+        });
+        if (rc) return rc;
+        if (red) {
+            rc = call_reducer(red, b.Rmap, MN, s);
+            if (rc) return rc;
+        }
+        rc = ln.run(ADMM_K_ADJ, [&] {
+            hipLaunchKernelGGL(g::iso_adj_b_kernel, p.gl, dim3(256), p.lup, s, b.wbar, r.sbi, r.sk1, r.nrm1, b.Rmap, r.sbo,
+                               v.spec0, v.twM, p.pM, N, p.T, v.prm);
+        });
+        if (rc) return rc;
+    }
+    return ADMM_OK;
+}
+
+// The fused reverse sweep: one workgroup per plane runs all K steps (plane256_adj_kernel).  traj: the forward's s_k, or
+// (masks) their ST mask bits; with rho_bar (xK given) D x_K goes to dxK first, lane-native: it and s_k enter rho_bar's
+// <D vbar, D x_k> only.  part: 2 doubles per plane.
+int fused_reverse(Launcher& ln, const float* x_bar, const void* tabs, const void* traj, bool masks, const float* xK,
+                  float4* dxK, float4* sbar, float2* vsl, float* vout, double* part, const float* prm, int K, size_t planes,
+                  const plane::Branches* br = nullptr) {
+    namespace pk = admm::plane;
+    hipStream_t s = ln.s;
+    if (!xK) dxK = nullptr;
+    if (dxK) {
+        int rc = ln.run(ADMM_K_PREP, [&] { return pk::launch_dx_lane(xK, dxK, planes, s, br); });
+        if (rc) return rc;
+    }
+    return ln.run(ADMM_K_ADJ, [&] {
+        return pk::launch_plane_adj(x_bar, tabs, traj, dxK, sbar, vsl, vout, part, prm, K, planes, s, br, masks);
+    });
+}
+
+// The fused isotropic sweep (plane_iso.hip) over f's planes: per step one plane256_isoadj_kernel (B phase of step
+// k + 1, column phase, A phase of step k) and, for k >= 2, one iso_radj_kernel (R_k per branch, tau_bar rows: step k's
+// at (K - k) x 512 of each branch's block, part_branch doubles apart).  f.ql: the per plane R partials.
+int fused_iso_reverse(Launcher& ln, const FusedIso& f, const float* x_bar, float2* vbuf, float4* sbar, float2* rmap,
+                      float2* vsl, float* vout, double* part, size_t part_branch, int K,
+                      const admm_batch_reducer* red = nullptr) {
+    namespace pk = admm::plane;
+    hipStream_t s = ln.s;
+    for (int k = K; k >= 1; --k) {
+        int rc = ln.run(ADMM_K_ADJ, [&] {
+            return pk::launch_plane_isoadj(x_bar, f.tabs, f.st, f.tslot, f.nrm, f.nslot, vbuf, sbar, rmap, f.ql, vsl, vout,
+                                           f.prm, k, K, f.planes, s, f.br);
+        });
+        if (rc) return rc;
+        if (k == 1) break;
+        rc = ln.run(ADMM_K_NORM, [&] {
+            return pk::launch_iso_radj(f.ql, rmap, f.nrm + (size_t)(k - 2) * f.nslot, part + (size_t)(K - k) * 512 * 2,
+                                       part_branch, f.prm, f.planes, s, f.br);
+        });
+        if (rc) return rc;
+        // sharded batch: tau_bar above used this shard's R (shard contributions add up); sbar needs the whole
+        // batch's R
+        if (red) {
+            rc = call_reducer(red, reinterpret_cast<float*>(rmap), (size_t)kMultiM * kMultiN, s);
+            if (rc) return rc;
+        }
+    }
+    return ADMM_OK;
+}
+
+// One-grid call: each branch's partial rows (bstride doubles apart) -> its (rho_bar, tau_bar) sums -> lambda_bar[i],
+// rho_bar[i]; then y_bar = the sum of the branches' Vsum (n floats each)
+int branch_grads(Launcher& ln, const MultiView& v, size_t bstride, int rows, float* lambda_bar, float* rho_bar,
+                 const float* vsum, float* y_bar, size_t n, int nbr) {
+    hipStream_t s = ln.s;
+    for (int i = 0; i < nbr; ++i) {
+        int rc = ln.run(ADMM_K_FINAL, [&] { launch_reduce_cols(s, v.part + (size_t)i * bstride, v.rt + 2 * i, rows, 2, v.rtmp); });
+        if (rc) return rc;
+        rc = ln.run(ADMM_K_FINAL, [&] {
+            hipLaunchKernelGGL(admm::grads_final_kernel, dim3(1), dim3(64), 0, s, v.rt + 2 * i, (const double*)nullptr,
+                               (const double*)nullptr, 0, v.prm + 4 * i, lambda_bar ? lambda_bar + i : nullptr,
+                               rho_bar ? rho_bar + i : nullptr, (float*)nullptr);
+        });
+        if (rc) return rc;
+    }
+    if (!y_bar) return ADMM_OK;
+    return ln.run(ADMM_K_FINAL, [&] {
+        hipLaunchKernelGGL(admm::branch_sum_kernel, dim3(1024), dim3(kThreads), 0, s, vsum, y_bar, n, nbr);
+    });
+}
+
+#define HIPCHK(call)                                                                                   \
+    do {                                                                                               \
+        const hipError_t e_ = (call);                                                                  \
+        if (e_ != hipSuccess) return fail(ADMM_E_HIP, "%s: %s", #call, hipGetErrorString(e_));         \
+    } while (0)
+
+// Assembly of a single solve's gradients: the (rho_bar, tau_bar) rows, y_bar = H Vsum (or Vsum), h_bar = the
+// correlation of Vsum with y and the spectral term from Q, then lambda_bar / rho_bar / h_bar.
+// conv: the path's spectral convolution (two_pass_conv or gen_conv) of Vsum into y_bar; copy: y_bar is not already
+// Vsum (the fused sweeps write it there)
+template <typename Conv>
+int assemble_grads(Launcher& ln, const BwdView& v, const BwdLayout& bl, const float* y, float* y_bar, float* h_bar,
+                   float* lambda_bar, float* rho_bar, int M, int N, size_t planes, int kh, int kw, int red_rows, bool copy,
+                   Conv&& conv) {
+    hipStream_t s = ln.s;
+    const SweepBufs& b = v.b;
+    int rc = ln.run(ADMM_K_FINAL, [&] { launch_reduce_cols(s, b.part, v.rt, red_rows, 2, v.rtmp); });
+    if (rc) return rc;
+    if (kh > 0 && b.vsum) {
+        if (y_bar) {   // y_bar = H vsum  (centred circular convolution, spectrally)
+            rc = conv(b.vsum, y_bar);
+            if (rc) return rc;
+        }
+        if (h_bar) {
+            rc = ln.run(ADMM_K_FINAL, [&] {
+                const size_t lds = (size_t)(2 * bl.TY + kw - 1) * M * 4;
+                set_lds(admm::hbar_corr_kernel, lds);
+                hipLaunchKernelGGL(admm::hbar_corr_kernel, dim3(N / bl.TY, (unsigned)planes), dim3(kThreads), lds, s,
+                                   b.vsum, y, v.hpart, M, N, kh, kw, bl.TY);
+            });
+            if (rc) return rc;
+            rc = ln.run(ADMM_K_FINAL, [&] { launch_reduce_cols(s, v.hpart, v.hcorr, bl.nblk_corr, kh * kw, v.rtmp); });
+            if (rc) return rc;
+            const int nq = (M / 2 + 1) * N;
+            rc = ln.run(ADMM_K_FINAL, [&] {
+                hipLaunchKernelGGL(admm::reduce_planes_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, b.Qp, v.Q,
+                                   (int)planes, nq);
+            });
+            if (rc) return rc;
+            rc = ln.run(ADMM_K_FINAL, [&] {
+                hipLaunchKernelGGL(admm::hbarA_kernel, dim3(kh * kw), dim3(kThreads), 0, s, v.Q, v.f.C, v.sig, kh, M, N, v.hA);
+            });
+            if (rc) return rc;
+        }
+    } else if (copy && y_bar) {
+        HIPCHK(hipMemcpyAsync(y_bar, b.vsum, planes * (size_t)M * N * 4, hipMemcpyDeviceToDevice, s));
+    }
+    return ln.run(ADMM_K_FINAL, [&] {
+        const int nt = kh * kw > 1 ? kh * kw : 1;
+        hipLaunchKernelGGL(admm::grads_final_kernel, dim3((nt + 255) / 256), dim3(256), 0, s, v.rt, v.hcorr, v.hA, kh * kw,
+                           v.f.prm, lambda_bar, rho_bar, (h_bar && kh > 0) ? h_bar : nullptr);
+    });
+}
+
 int launch_backward(int phases, const float* y, const float* x_bar, float* y_bar, float* h_bar, float* lambda_bar,
                     float* rho_bar, int M, int N, size_t planes, const float* h, int kh, int kw,
                     const admm::ScalarSrc& sc, int iso, int maxit, float* x_out, void* workspace, void* stream,
                     const admm_batch_reducer* red, const PathPlan& plan, const BwdLayout& bl) {
     int rc = ADMM_OK;
-    const bool want_h = plan.want_h;
-    const bool ln_traj = plan.ln_traj;
-    const bool use_masks = plan.masks;
-    const bool iso_lane = plan.iso_lane;   // the fused isotropic sweep (no mask bits: s itself is needed)
     unsigned char* ws = static_cast<unsigned char*>(workspace);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     Launcher ln{s, g_prof.on, {}};
     const size_t MN = (size_t)M * N;
-    const int L = M / 2;
-    const bool gen = generic_shape(M, N);   // runtime-length path (admm_generic.hip, admm_generic_bwd.hip)
-    const int T = gen ? gen_T(M, N) : bwd_line_T(M, N, iso != 0);
-    const int KB = gen ? gen_KB(M, N) : column_KB(M, N);
-    float* prm = reinterpret_cast<float*>(ws + bl.f.prm);
     const int K = maxit;
     if (!x_out || (reinterpret_cast<uintptr_t>(x_out) & 15))
         return fail(ADMM_E_INVALID, "x_out (forward output of the recomputed solve) must be a 16-byte aligned device pointer");
-    float* xK = x_out;
-    hipError_t e;
-#define HIPCHK(call)                                                                           \
-    do {                                                                                       \
-        e = (call);                                                                            \
-        if (e != hipSuccess) return fail(ADMM_E_HIP, "%s: %s", #call, hipGetErrorString(e));   \
-    } while (0)
     if (K == 0) {
         if (phases & 2) {
             if (y_bar) HIPCHK(hipMemsetAsync(y_bar, 0, planes * MN * 4, s));
@@ -768,16 +1156,20 @@ int launch_backward(int phases, const float* y, const float* x_bar, float* y_bar
         if (phases & 1) HIPCHK(hipMemsetAsync(x_out, 0, planes * MN * 4, s));
         return ln.finish();
     }
+    // Vsum = sum_k vbar_k feeds y_bar and the h_bar correlation only: without either the sweeps skip it
+    const bool want_v = y_bar != nullptr || (h_bar != nullptr && kh > 0);
+    const BwdView v = view(ws, bl, kh > 0, iso != 0, plan.want_h, want_v, rho_bar ? x_out : nullptr);
+    const SweepBufs& b = v.b;
     // ---- forward with trajectory ----
     Traj tr;
-    tr.s = reinterpret_cast<float*>(ws + bl.traj_s);
-    tr.m = use_masks && !iso ? reinterpret_cast<unsigned*>(ws + bl.traj_s) : nullptr;
-    tr.iso_lane = iso_lane;
-    tr.v = want_h ? reinterpret_cast<float2*>(ws + bl.traj_v) : nullptr;
-    tr.sig = want_h ? reinterpret_cast<double2*>(ws + bl.sig) : nullptr;
-    tr.nrm = iso ? reinterpret_cast<float*>(ws + bl.traj_n) : nullptr;
+    tr.s = const_cast<float*>(b.traj);
+    tr.m = plan.masks && !iso ? at<unsigned>(ws, bl.traj_s) : nullptr;
+    tr.iso_lane = plan.iso_lane;   // the fused isotropic sweep (no mask bits: s itself is needed)
+    tr.v = b.v;
+    tr.sig = v.sig;
+    tr.nrm = const_cast<float*>(b.nrm);
     if (phases & 1) {
-        rc = run_forward(ln, y, xK, M, N, planes, h, kh, kw, sc, iso, K, ws, bl.f, tr, red, plan.fwd);
+        rc = run_forward(ln, y, x_out, M, N, planes, h, kh, kw, sc, iso, K, ws, bl.f, tr, red, plan.fwd);
         if (rc) return rc;
     }
     if (!(phases & 2)) return ln.finish();
@@ -785,527 +1177,60 @@ int launch_backward(int phases, const float* y, const float* x_bar, float* y_bar
     // used as is -- the reverse sweep must differentiate the trajectory that was recorded, even if a
     // device-resident lambda / rho has changed since (host values were checked against the tag above)
     // ---- reverse sweep ----
-    float2* twM = reinterpret_cast<float2*>(ws + bl.f.twM);
-    float2* twN = reinterpret_cast<float2*>(ws + bl.f.twN);
-    float* Ct = reinterpret_cast<float*>(ws + bl.f.C);
-    float2* Gt = kh > 0 ? reinterpret_cast<float2*>(ws + bl.f.G) : nullptr;
-    float2* specA = reinterpret_cast<float2*>(ws + bl.f.spec0);
-    float2* specB = reinterpret_cast<float2*>(ws + bl.f.spec1);
-    float* sb[2] = {reinterpret_cast<float*>(ws + bl.sbA), reinterpret_cast<float*>(ws + bl.sbB)};
-    // Vsum = sum_k vbar_k feeds y_bar and the h_bar correlation only: without either the sweep skips it
-    const bool want_v = y_bar != nullptr || (h_bar != nullptr && kh > 0);
-    float* vsum = want_v ? reinterpret_cast<float*>(ws + bl.vsum) : nullptr;
-    // s_k and D x_K enter rho_bar's <D vbar, D x_k> only (fused and iso sweeps skip them without rho_bar)
-    const bool want_rho = rho_bar != nullptr;
-    double* rpart = reinterpret_cast<double*>(ws + bl.rpart);
-    double* Qp = want_h ? reinterpret_cast<double*>(ws + bl.Qp) : nullptr;
-    const size_t sstride = planes * 2 * MN;
-    const size_t clds = column_lds(N, KB), flds = fwdinv_lds(M, T);
-    const size_t alds = line_lds(M, T) + 8 * 16;
-    const dim3 gl(N / T, (unsigned)planes), gc(L / KB, (unsigned)planes);
-    // fused reverse sweep: one workgroup per plane runs all K steps (plane256_adj_kernel)
-    const bool fused_adj = plan.bwd == ADMM_PATH_SWEEP_FUSED;
+    // the fused sweeps write Vsum straight into y_bar without a PSF
+    float* vout = !want_v ? nullptr : kh > 0 ? b.vsum : y_bar;
+    const bool fused = plan.bwd == ADMM_PATH_SWEEP_FUSED || plan.bwd == ADMM_PATH_SWEEP_FUSED_ISO;
     int red_rows = K * bl.nblk_line;   // rows of (rho_bar, tau_bar) partials
-    if (fused_adj) {
-        namespace pk = admm::plane;
-        float4* dxK = want_rho ? reinterpret_cast<float4*>(sb[1]) : nullptr;
-        float* vout = !want_v ? nullptr : kh > 0 ? vsum : y_bar;
-        if (want_rho) {
-            rc = ln.run(ADMM_K_PREP, [&] { return pk::launch_dx_lane(xK, dxK, planes, s); });
-            if (rc) return rc;
-        }
-        rc = ln.run(ADMM_K_ADJ, [&] {
-            return pk::launch_plane_adj(x_bar, ws + bl.f.F, tr.m ? static_cast<const void*>(tr.m) : tr.s, dxK,
-                                       reinterpret_cast<float4*>(sb[0]), specA, vout, rpart, prm, K, planes, s,
-                                       nullptr, tr.m != nullptr);
-        });
-        if (rc) return rc;
-        red_rows = (int)planes;
-    } else if (iso_lane) {
-        // isotropic fused sweep: per step one plane256_isoadj_kernel (B phase of step k+1, column phase, A phase
-        // of step k) and one iso_radj_kernel (R_k over the batch, tau_bar rows); rows of step k at (K - k) x 512
-        namespace pk = admm::plane;
-        const size_t kE = MN / 2;   // lane-native float2 elements per plane
-        float4* trs = reinterpret_cast<float4*>(tr.s);
-        const float2* trn = reinterpret_cast<const float2*>(tr.nrm);
-        float2* vbuf = reinterpret_cast<float2*>(ws + bl.wbar);
-        float2* rmap = reinterpret_cast<float2*>(ws + bl.Rmap);
-        float2* rpl = specB;    // per plane R partials (the forward's q partials, free now)
-        float2* vsl = specA;    // lane-native Vsum (the forward's H^T y, free now)
-        float* vout = !want_v ? nullptr : kh > 0 ? vsum : y_bar;
-        HIPCHK(hipMemsetAsync(rpart, 0, (size_t)(K > 1 ? K - 1 : 1) * 512 * 2 * 8, s));
-        for (int k = K; k >= 1; --k) {
-            rc = ln.run(ADMM_K_ADJ, [&] {
-                return pk::launch_plane_isoadj(x_bar, ws + bl.f.F, trs, planes * kE, trn, kE, vbuf,
-                                               reinterpret_cast<float4*>(sb[0]), rmap, rpl, vsl, vout, prm, k, K, planes, s);
-            });
-            if (rc) return rc;
-            if (k >= 2) {
-                rc = ln.run(ADMM_K_NORM, [&] {
-                    return pk::launch_iso_radj(rpl, rmap, trn + (size_t)(k - 2) * kE, rpart + (size_t)(K - k) * 512 * 2, 0,
-                                               prm, planes, s);
-                });
-                if (rc) return rc;
-                // sharded batch: tau_bar above used this shard's R (shard contributions add up); sbar needs the
-                // whole batch's R
-                if (red) {
-                    rc = call_reducer(red, reinterpret_cast<float*>(rmap), MN, s);
-                    if (rc) return rc;
-                }
-            }
-        }
-        red_rows = (K > 1 ? K - 1 : 1) * 512;
-    } else if (want_v) {
-        HIPCHK(hipMemsetAsync(vsum, 0, planes * MN * 4, s));
+    if (!fused) {
+        if (b.vsum) HIPCHK(hipMemsetAsync(b.vsum, 0, planes * MN * 4, s));
+        // k = 1 launches no ISO_ADJ_R: its partial rows must read as zero
+        if (iso) HIPCHK(hipMemsetAsync(b.part, 0, (size_t)K * bl.nblk_line * 2 * 8, s));
+        if (b.Qp) HIPCHK(hipMemsetAsync(b.Qp, 0, planes * (size_t)(M / 2 + 1) * N * 8, s));
     }
-    float* wbar = iso ? reinterpret_cast<float*>(ws + bl.wbar) : nullptr;
-    float* Rmap = iso ? reinterpret_cast<float*>(ws + bl.Rmap) : nullptr;
-    float* Rpart = iso ? reinterpret_cast<float*>(ws + bl.Rpart) : nullptr;
-    const int ngi = iso_ngroups(planes);
-    // k = 1 launches no ISO_ADJ_R: its partial rows must read as zero
-    if (iso && !iso_lane) HIPCHK(hipMemsetAsync(rpart, 0, (size_t)K * bl.nblk_line * 2 * 8, s));
-    if (Qp) HIPCHK(hipMemsetAsync(Qp, 0, planes * (size_t)(L + 1) * N * 8, s));
-    if (gen) {
-        // ---- runtime-length reverse sweep (admm_generic_bwd.hip): column, line inverse -> vbar_k in
-        // HBM, then the line adjoint (aniso) or ISO_ADJ_A -> ISO_ADJ_R -> ISO_ADJ_B ----
-        namespace g = admm::gen;
-        const int H = M / 2 + 1;
-        const g::FPlan pM = make_fplan(M), pN = make_fplan(N);
-        const dim3 ggl(gen_nb(N, T), (unsigned)planes), ggc((H + KB - 1) / KB, (unsigned)planes);
-        const size_t lfw = gen_lds_line(M, T, false), lup = gen_lds_line(M, T, true);
-        const size_t lcol = gen_lds_col(N, KB);
-        set_lds(g::line_fwd_kernel, lfw);
-        set_lds(g::line_inv_kernel, lfw);
-        set_lds(g::line_adj_kernel, lup);
-        set_lds(g::iso_adj_b_kernel, lup);
-        set_lds(g::column_kernel, lcol);
-        float* vb = reinterpret_cast<float*>(ws + bl.f.xg);
-        rc = ln.run(ADMM_K_PREP, [&] { hipLaunchKernelGGL(g::line_fwd_kernel, ggl, dim3(256), lfw, s, x_bar, specA, twM, pM, N, T); });
-        if (rc) return rc;
-        for (int k = K; k >= 1; --k) {
-            float2* vs = want_h ? tr.v + (size_t)(k - 1) * planes * N * H : nullptr;
-            rc = ln.run(ADMM_K_COLUMN, [&] {
-                hipLaunchKernelGGL(g::column_kernel, ggc, dim3(256), lcol, s, specA, specB, Ct, Gt, twN, pN, H, KB,
-                                   want_h ? 8 : 0, 1.0f, vs, Qp);
-            });
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_LINE, [&] { hipLaunchKernelGGL(g::line_inv_kernel, ggl, dim3(256), lfw, s, specB, vb, twM, pM, N, T); });
-            if (rc) return rc;
-            const float* sk1 = k >= 2 ? tr.s + (size_t)(k - 2) * sstride : nullptr;
-            const float* skk = k < K ? tr.s + (size_t)(k - 1) * sstride : nullptr;
-            const float* sbi = k < K ? sb[k & 1] : nullptr;
-            float* sbo = sb[(k & 1) ^ 1];
-            double* rp = rpart + (size_t)(K - k) * bl.nblk_line * 2;
-            if (!iso) {
-                rc = ln.run(ADMM_K_ADJ, [&] {
-                    hipLaunchKernelGGL(g::line_adj_kernel, ggl, dim3(256), lup, s, vb, sk1, skk, xK, sbi, sbo, vsum, specA,
-                                       rp, twM, pM, N, T, prm);
-                });
-                if (rc) return rc;
-                continue;
-            }
-            const float* nrm1 = k >= 2 ? tr.nrm + (size_t)(k - 2) * MN : nullptr;
-            rc = ln.run(ADMM_K_ADJ, [&] {
-                hipLaunchKernelGGL(g::iso_adj_a_kernel, dim3(gen_nb(N, T), (unsigned)ngi), dim3(256), (size_t)T * M * 4, s, vb,
-                                   sk1, skk, xK, nrm1, sbi, wbar, vsum, Rpart, rp, M, N, (int)planes, iso_group(planes),
-                                   T, prm);
-            });
-            if (rc) return rc;
-            if (k == 1) break;
-            rc = ln.run(ADMM_K_NORM, [&] {
-                hipLaunchKernelGGL(admm::iso_adj_r_kernel, dim3(kIsoAdjRBlocks), dim3(kThreads), 0, s, Rpart, Rmap,
-                                   nrm1, ngi, MN, prm, rp + (size_t)bl.nblk_isoA * 2);
-            });
-            if (rc) return rc;
-            if (red) {
-                rc = call_reducer(red, Rmap, MN, s);
-                if (rc) return rc;
-            }
-            rc = ln.run(ADMM_K_ADJ, [&] {
-                hipLaunchKernelGGL(g::iso_adj_b_kernel, ggl, dim3(256), lup, s, wbar, sbi, sk1, nrm1, Rmap, sbo, specA,
-                                   twM, pM, N, T, prm);
-            });
-            if (rc) return rc;
+    const bool gen = generic_shape(M, N);   // runtime-length path (admm_generic.hip, admm_generic_bwd.hip)
+    const GenPass gp = gen ? gen_pass(M, N, planes, false) : GenPass{};
+    auto grid = [&] {   // the 2-pass grid of the sweep and of y_bar = H Vsum (power-of-two shapes)
+        TwoPass c = two_pass_single(ln, M, N, planes, bwd_line_T(M, N, iso != 0), v.f);
+        c.rows = bl.nblk_line, c.r_off = bl.nblk_isoA;
+        return c;
+    };
+    switch (plan.bwd) {
+        case ADMM_PATH_SWEEP_FUSED:   // D x_K in the second sbar buffer, lane-native Vsum in spec0
+            rc = fused_reverse(ln, x_bar, v.f.F, b.traj, tr.m != nullptr, b.xK, reinterpret_cast<float4*>(b.sb[1]),
+                               reinterpret_cast<float4*>(b.sb[0]), v.f.spec0, vout, b.part, v.f.prm, K, planes);
+            red_rows = (int)planes;
+            break;
+        case ADMM_PATH_SWEEP_FUSED_ISO: {
+            // vbar in the wbar slot, per plane R partials in spec1 (the forward's q partials, free now), lane-native
+            // Vsum in spec0 (the forward's H^T y, free now); rows of step k at (K - k) x 512
+            const size_t kE = MN / 2;   // lane-native float2 elements per plane
+            red_rows = (K > 1 ? K - 1 : 1) * 512;
+            HIPCHK(hipMemsetAsync(b.part, 0, (size_t)red_rows * 2 * 8, s));
+            const FusedIso f{v.f.F, v.f.prm, planes, nullptr, reinterpret_cast<float4*>(tr.s), planes * kE,
+                             reinterpret_cast<float2*>(tr.nrm), kE, nullptr, v.f.spec1};
+            rc = fused_iso_reverse(ln, f, x_bar, at<float2>(ws, bl.wbar), reinterpret_cast<float4*>(b.sb[0]),
+                                   at<float2>(ws, bl.Rmap), v.f.spec0, vout, b.part, 0, K, red);
+            break;
         }
-    } else if (!fused_adj && !iso_lane) {
-        rc = ln.run(ADMM_K_PREP, [&] { return launch_line_fwd(L, T, gl, flds, s, x_bar, specA, twM, N); });
-        if (rc) return rc;
+        case ADMM_PATH_SWEEP_RUNTIME:
+        case ADMM_PATH_SWEEP_RUNTIME_ISO:
+            rc = runtime_reverse(ln, gp, v.f, b, x_bar, x_out, K, iso != 0, bl.nblk_line, bl.nblk_isoA, red);
+            break;
+        default:
+            rc = two_pass_reverse(grid(), b, x_bar, K, iso != 0, plan.ln_traj, red);
     }
-    for (int k = (fused_adj || gen || iso_lane) ? 0 : K; k >= 1; --k) {
-        float2* vs = want_h ? tr.v + (size_t)(k - 1) * planes * N * L : nullptr;
-        rc = ln.run(ADMM_K_COLUMN, [&] {
-            return launch_column(N, want_h ? 4 : 0, gc, clds, s, specA, specB, Ct, Gt, twN, L, KB, 1.0f, vs, Qp);
-        });
-        if (rc) return rc;
-        const float* sk1 = k >= 2 ? tr.s + (size_t)(k - 2) * sstride : nullptr;
-        const float* skk = k < K ? tr.s + (size_t)(k - 1) * sstride : nullptr;
-        const float* sbi = k < K ? sb[k & 1] : nullptr;
-        float* sbo = sb[(k & 1) ^ 1];
-        double* rp = rpart + (size_t)(K - k) * bl.nblk_line * 2;
-        if (!iso) {
-            rc = ln.run(ADMM_K_ADJ, [&] {
-                return launch_line_adj(L, T, gl, alds, s, specB, sk1, want_rho ? skk : nullptr, want_rho ? xK : nullptr,
-                                       sbi, sbo, vsum, specA, rp, twM, N, prm,
-                                k == 1 ? 1 : 0, k == K ? 1 : 0, ln_traj);
-            });
-            if (rc) return rc;
-            continue;
-        }
-        // isotropic: ISO_ADJ_A (plane groups) -> ISO_ADJ_R (batch R map, tau_bar) -> ISO_ADJ_B (per plane)
-        const float* nrm1 = k >= 2 ? tr.nrm + (size_t)(k - 2) * MN : nullptr;
-        rc = ln.run(ADMM_K_ADJ, [&] {
-            return launch_iso_adj_a(L, T, dim3(N / T, (unsigned)ngi), iso_a_lds(M, T) + 8 * 16, s, specB, sk1,
-                             want_rho ? skk : nullptr, want_rho ? xK : nullptr,
-                             nrm1, sbi, wbar, vsum, Rpart, rp, twM, N, (int)planes, iso_group(planes), prm,
-                             k == 1 ? 1 : 0, k == K ? 1 : 0);
-        });
-        if (rc) return rc;
-        if (k == 1) break;
-        rc = ln.run(ADMM_K_NORM, [&] {
-            hipLaunchKernelGGL(admm::iso_adj_r_kernel, dim3(kIsoAdjRBlocks), dim3(kThreads), 0, s, Rpart, Rmap, nrm1,
-                               ngi, MN, prm, rp + (size_t)bl.nblk_isoA * 2);
-        });
-        if (rc) return rc;
-        // sharded batch: tau_bar above used this shard's R (shard contributions add up, like every other
-        // parameter gradient); sbar needs the whole batch's R
-        if (red) {
-            rc = call_reducer(red, Rmap, MN, s);
-            if (rc) return rc;
-        }
-        rc = ln.run(ADMM_K_ADJ, [&] {
-            return launch_iso_adj_b(L, T, gl, iso_b_lds(M, T), s, wbar, sbi, sk1, nrm1, Rmap, sbo, specA, twM, N, prm);
-        });
-        if (rc) return rc;
-    }
+    if (rc) return rc;
     // ---- assembly ----
-    double* rt = reinterpret_cast<double*>(ws + bl.rt);
-    rc = ln.run(ADMM_K_FINAL, [&] {
-        launch_reduce_cols(s, rpart, rt, red_rows, 2, reinterpret_cast<double*>(ws + bl.rtmp));
-    });
+    rc = assemble_grads(ln, v, bl, y, y_bar, h_bar, lambda_bar, rho_bar, M, N, planes, kh, kw, red_rows, !fused,
+                        [&](const float* src, float* dst) {
+                            return gen ? gen_conv(ln, gp, v.f, ADMM_K_FINAL, 2, src, dst)
+                                       : two_pass_conv(grid(), ADMM_K_FINAL, 2, src, dst);
+                        });
     if (rc) return rc;
-    double* hcorr = kh > 0 ? reinterpret_cast<double*>(ws + bl.hcorr) : nullptr;
-    double* hA = want_h ? reinterpret_cast<double*>(ws + bl.hA) : nullptr;
-    if (kh > 0 && want_v) {
-        // y_bar = H vsum  (centred circular convolution, spectrally)
-        if (y_bar && gen) {
-            namespace g = admm::gen;
-            const int H = M / 2 + 1;
-            const g::FPlan pM = make_fplan(M), pN = make_fplan(N);
-            const dim3 ggl(gen_nb(N, T), (unsigned)planes), ggc((H + KB - 1) / KB, (unsigned)planes);
-            const size_t lfw = gen_lds_line(M, T, false), lcol = gen_lds_col(N, KB);
-            rc = ln.run(ADMM_K_FINAL, [&] { hipLaunchKernelGGL(g::line_fwd_kernel, ggl, dim3(256), lfw, s, vsum, specA, twM, pM, N, T); });
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_FINAL, [&] {
-                hipLaunchKernelGGL(g::column_kernel, ggc, dim3(256), lcol, s, specA, specB, Ct, Gt, twN, pN, H, KB, 2, 1.0f,
-                                   (float2*)nullptr, (double*)nullptr);
-            });
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_FINAL, [&] { hipLaunchKernelGGL(g::line_inv_kernel, ggl, dim3(256), lfw, s, specB, y_bar, twM, pM, N, T); });
-            if (rc) return rc;
-        } else if (y_bar) {
-            rc = ln.run(ADMM_K_FINAL, [&] { return launch_line_fwd(L, T, gl, flds, s, vsum, specA, twM, N); });
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_FINAL, [&] { return launch_column(N, 2, gc, clds, s, specA, specB, Ct, Gt, twN, L, KB, 1.0f); });
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_FINAL, [&] { return launch_line_inv(L, T, gl, flds, s, specB, y_bar, twM, N); });
-            if (rc) return rc;
-        }
-        if (h_bar) {
-            double* hpart = reinterpret_cast<double*>(ws + bl.hpart);
-            rc = ln.run(ADMM_K_FINAL, [&] {
-                const size_t lds = (size_t)(2 * bl.TY + kw - 1) * M * 4;
-                set_lds(admm::hbar_corr_kernel, lds);
-                hipLaunchKernelGGL(admm::hbar_corr_kernel, dim3(N / bl.TY, (unsigned)planes), dim3(kThreads), lds, s,
-                                   vsum, y, hpart, M, N, kh, kw, bl.TY);
-            });
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_FINAL, [&] {
-                launch_reduce_cols(s, hpart, hcorr, bl.nblk_corr, kh * kw, reinterpret_cast<double*>(ws + bl.rtmp));
-            });
-            if (rc) return rc;
-            double* Q = reinterpret_cast<double*>(ws + bl.Q);
-            const int nq = (L + 1) * N;
-            rc = ln.run(ADMM_K_FINAL, [&] {
-                hipLaunchKernelGGL(admm::reduce_planes_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, Qp, Q,
-                                   (int)planes, nq);
-            });
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_FINAL, [&] {
-                hipLaunchKernelGGL(admm::hbarA_kernel, dim3(kh * kw), dim3(kThreads), 0, s, Q, Ct, tr.sig, kh, M, N,
-                                   hA);
-            });
-            if (rc) return rc;
-        }
-    } else if (!fused_adj && !iso_lane && y_bar) {   // (the fused sweeps wrote Vsum straight into y_bar)
-        HIPCHK(hipMemcpyAsync(y_bar, vsum, planes * MN * 4, hipMemcpyDeviceToDevice, s));
-    }
-    rc = ln.run(ADMM_K_FINAL, [&] {
-        const int nt = kh * kw > 1 ? kh * kw : 1;
-        hipLaunchKernelGGL(admm::grads_final_kernel, dim3((nt + 255) / 256), dim3(256), 0, s, rt, hcorr, hA, kh * kw,
-                           prm, lambda_bar, rho_bar, (h_bar && kh > 0) ? h_bar : nullptr);
-    });
-    if (rc) return rc;
-#undef HIPCHK
     return ln.finish();
 }
 
-// ---- several branches below the plane-count rule: the 2-pass kernels over every branch's planes ----
-// Grid plane q = i ppb + loc is branch i's solve of input plane loc (y shared, x_out / x_bar in the chcat layout:
-// the line transforms map planes, admm_kernels.hip PlaneMap); per branch its C table, {tau, rho, lambda}, f map,
-// |s| slots, R map and plane groups.  The step sequences are run_forward's / launch_backward's 2-pass ones.
-Branches multi2_branches(int P, int B, int nbr) { return Branches{P * B, nbr, P, (unsigned)(multi_C_bytes() / 4), 4u}; }
-
-int run_multi_2pass_iso_fwd(Launcher& ln, const float* y, float* x_out, int P, int B, int nbr, int maxit, bool rec,
-                            unsigned char* ws, size_t planes, const MultiLayout& Ly) {
-    hipStream_t s = ln.s;
-    constexpr int M = kMultiM, N = kMultiN, L = M / 2;
-    const size_t MN = (size_t)M * N, ppb = (size_t)P * B, sstride = planes * 2 * MN;
-    const Branches br = multi2_branches(P, B, nbr);
-    const int T = line_T(M, N), KB = column_KB(M, N);
-    const size_t flds = fwdinv_lds(M, T), clds = column_lds(N, KB);
-    const dim3 gl(N / T, (unsigned)planes), gc(L / KB, (unsigned)planes);
-    float2* twM = reinterpret_cast<float2*>(ws + Ly.twM);
-    float2* twN = reinterpret_cast<float2*>(ws + Ly.twN);
-    const float* Ct = reinterpret_cast<const float*>(ws + Ly.C);
-    const float* prm = reinterpret_cast<const float*>(ws + Ly.prm);
-    float2* spec0 = reinterpret_cast<float2*>(ws + Ly.spec0);
-    float2* spec1 = reinterpret_cast<float2*>(ws + Ly.spec1);
-    float* fmap = reinterpret_cast<float*>(ws + Ly.fmap);
-    float* qpart = reinterpret_cast<float*>(ws + Ly.qpart);
-    float* traj = rec ? reinterpret_cast<float*>(ws + Ly.traj) : nullptr;
-    float* nrm = rec ? reinterpret_cast<float*>(ws + Ly.nrm) : nullptr;
-    float* sA = rec ? nullptr : reinterpret_cast<float*>(ws + Ly.sA);
-    // H^T y = y (no PSF) in the spectral domain, as run_forward's 2-pass kernels: Y_h = F y per grid plane (the
-    // hln slot, unused by the 2-pass grid), added by every column pass; iteration 1 transforms a zero spectrum
-    float2* yh = reinterpret_cast<float2*>(ws + Ly.hln);
-    int rc = ln.run(ADMM_K_PREP, [&] { return launch_line_fwd(L, T, gl, flds, s, y, spec0, twM, N, br, kMapIn); });
-    if (rc) return rc;
-    rc = ln.run(ADMM_K_PREP, [&] {
-        return launch_column(N, 5, gc, clds, s, spec0, spec1, Ct, nullptr, twN, L, KB, 1.0f, nullptr, nullptr, br, yh);
-    });
-    if (rc) return rc;
-    if (hipMemsetAsync(spec0, 0, planes * MN * 4, s) != hipSuccess) return fail(ADMM_E_HIP, "hipMemsetAsync");
-    for (int it = 1; it <= maxit; ++it) {
-        rc = ln.run(ADMM_K_COLUMN, [&] {
-            return launch_column(N, 6, gc, clds, s, spec0, spec1, Ct, nullptr, twN, L, KB, 1.0f, nullptr, nullptr, br, yh);
-        });
-        if (rc) return rc;
-        if (it == maxit) {
-            rc = ln.run(ADMM_K_FINAL, [&] { return launch_line_inv(L, T, gl, flds, s, spec1, x_out, twM, N, br, kMapOut); });
-            if (rc) return rc;
-            break;
-        }
-        // recording: s_it into slot it - 1 (the first iteration reads no s), |s_it| into norm slot it - 1
-        float* sn = rec ? traj + (size_t)(it - 1) * sstride : sA;
-        const float* so = rec ? (it >= 2 ? traj + (size_t)(it - 2) * sstride : sn) : sA;
-        float* nrm_out = rec ? nrm + (size_t)(it - 1) * nbr * MN : nullptr;
-        rc = ln.run(ADMM_K_LINE, [&] {
-            return launch_iso_a(L, T, dim3(N / T, (unsigned)(nbr * Ly.ngb)), iso_a_lds(M, T), s, spec1, so, sn, fmap,
-                                qpart, twM, N, (int)ppb, Ly.G, it == 1 ? 1 : 0, Ly.ngb);
-        });
-        if (rc) return rc;
-        rc = ln.run(ADMM_K_NORM, [&] {
-            hipLaunchKernelGGL(admm::iso_r_kernel, dim3((unsigned)std::min<size_t>((MN + 63) / 64, 2048), (unsigned)nbr),
-                               dim3(kThreads), 0, s, qpart, fmap, Ly.ngb, MN, prm, nrm_out, 4u);
-        });
-        if (rc) return rc;
-        rc = ln.run(ADMM_K_LINE, [&] {
-            return launch_iso_b(L, T, gl, iso_b_lds(M, T), s, sn, fmap, nullptr, spec0, twM, N, prm, br);
-        });
-        if (rc) return rc;
-    }
-    return ADMM_OK;
-}
-
-int run_multi_2pass_iso_bwd(Launcher& ln, const float* x_bar, float* y_bar, float* lambda_bar, int P, int B, int nbr,
-                            int K, unsigned char* ws, size_t planes, const MultiLayout& Ly) {
-    hipStream_t s = ln.s;
-    constexpr int M = kMultiM, N = kMultiN, L = M / 2;
-    const size_t MN = (size_t)M * N, ppb = (size_t)P * B, sstride = planes * 2 * MN;
-    const Branches br = multi2_branches(P, B, nbr);
-    const int T = bwd_line_T(M, N, true), KB = column_KB(M, N);
-    const size_t flds = fwdinv_lds(M, T), clds = column_lds(N, KB);
-    const dim3 gl(N / T, (unsigned)planes), gc(L / KB, (unsigned)planes);
-    float2* twM = reinterpret_cast<float2*>(ws + Ly.twM);
-    float2* twN = reinterpret_cast<float2*>(ws + Ly.twN);
-    const float* Ct = reinterpret_cast<const float*>(ws + Ly.C);
-    const float* prm = reinterpret_cast<const float*>(ws + Ly.prm);
-    float2* specA = reinterpret_cast<float2*>(ws + Ly.spec0);
-    float2* specB = reinterpret_cast<float2*>(ws + Ly.spec1);
-    const float* traj = reinterpret_cast<const float*>(ws + Ly.traj);
-    const float* nrm = reinterpret_cast<const float*>(ws + Ly.nrm);
-    float* sb[2] = {reinterpret_cast<float*>(ws + Ly.sbA), reinterpret_cast<float*>(ws + Ly.sbB)};
-    float* vsum = y_bar ? reinterpret_cast<float*>(ws + Ly.vsum) : nullptr;
-    float* wbar = reinterpret_cast<float*>(ws + Ly.wbar);
-    float* Rmap = reinterpret_cast<float*>(ws + Ly.rmap);
-    float* Rpart = reinterpret_cast<float*>(ws + Ly.Rpart);
-    double* part = reinterpret_cast<double*>(ws + Ly.part);
-    hipError_t e = hipMemsetAsync(part, 0, (size_t)nbr * Ly.pbs * 8, s);   // k = 1 launches no ISO_ADJ_R
-    if (e == hipSuccess && vsum) e = hipMemsetAsync(vsum, 0, planes * MN * 4, s);
-    if (e != hipSuccess) return fail(ADMM_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-    int rc = ln.run(ADMM_K_PREP, [&] { return launch_line_fwd(L, T, gl, flds, s, x_bar, specA, twM, N, br, kMapOut); });
-    if (rc) return rc;
-    for (int k = K; k >= 1; --k) {
-        rc = ln.run(ADMM_K_COLUMN, [&] {
-            return launch_column(N, 0, gc, clds, s, specA, specB, Ct, nullptr, twN, L, KB, 1.0f, nullptr, nullptr, br);
-        });
-        if (rc) return rc;
-        const float* sk1 = k >= 2 ? traj + (size_t)(k - 2) * sstride : nullptr;
-        const float* sbi = k < K ? sb[k & 1] : nullptr;
-        float* sbo = sb[(k & 1) ^ 1];
-        double* rp = part + (size_t)(K - k) * Ly.rows_b * 2;
-        const float* nrm1 = k >= 2 ? nrm + (size_t)(k - 2) * nbr * MN : nullptr;
-        rc = ln.run(ADMM_K_ADJ, [&] {
-            return launch_iso_adj_a(L, T, dim3(N / T, (unsigned)(nbr * Ly.ngb)), iso_a_lds(M, T) + 8 * 16, s, specB, sk1,
-                                    nullptr, nullptr, nrm1, sbi, wbar, vsum, Rpart, rp, twM, N, (int)ppb, Ly.G, prm,
-                                    k == 1 ? 1 : 0, k == K ? 1 : 0, br, Ly.ngb, Ly.pbs);
-        });
-        if (rc) return rc;
-        if (k == 1) break;
-        rc = ln.run(ADMM_K_NORM, [&] {
-            hipLaunchKernelGGL(admm::iso_adj_r_kernel, dim3(kIsoAdjRBlocks, (unsigned)nbr), dim3(kThreads), 0, s, Rpart,
-                               Rmap, nrm1, Ly.ngb, MN, prm, rp + (size_t)Ly.nblk_a * 2, 4u, Ly.pbs);
-        });
-        if (rc) return rc;
-        rc = ln.run(ADMM_K_ADJ, [&] {
-            return launch_iso_adj_b(L, T, gl, iso_b_lds(M, T), s, wbar, sbi, sk1, nrm1, Rmap, sbo, specA, twM, N, prm, br);
-        });
-        if (rc) return rc;
-    }
-    double* rt = reinterpret_cast<double*>(ws + Ly.rt);
-    for (int i = 0; i < nbr; ++i) {
-        rc = ln.run(ADMM_K_FINAL, [&] {
-            launch_reduce_cols(s, part + (size_t)i * Ly.pbs, rt + 2 * i, K * Ly.rows_b, 2,
-                               reinterpret_cast<double*>(ws + Ly.rtmp));
-        });
-        if (rc) return rc;
-        rc = ln.run(ADMM_K_FINAL, [&] {
-            hipLaunchKernelGGL(admm::grads_final_kernel, dim3(1), dim3(64), 0, s, rt + 2 * i, (const double*)nullptr,
-                               (const double*)nullptr, 0, prm + 4 * i, lambda_bar ? lambda_bar + i : nullptr,
-                               (float*)nullptr, (float*)nullptr);
-        });
-        if (rc) return rc;
-    }
-    if (y_bar) {
-        rc = ln.run(ADMM_K_FINAL, [&] {
-            hipLaunchKernelGGL(admm::branch_sum_kernel, dim3(1024), dim3(kThreads), 0, s, vsum, y_bar, ppb * MN, nbr);
-        });
-        if (rc) return rc;
-    }
-    return ADMM_OK;
-}
-
-int run_multi_2pass_fwd(Launcher& ln, const float* y, float* x_out, int P, int B, int nbr, int maxit, bool rec,
-                        unsigned char* ws, size_t planes, const MultiLayout& Ly) {
-    hipStream_t s = ln.s;
-    constexpr int M = kMultiM, N = kMultiN, L = M / 2;
-    const size_t MN = (size_t)M * N, sstride = planes * 2 * MN;
-    const Branches br = multi2_branches(P, B, nbr);
-    const int T = line_T(M, N), KB = column_KB(M, N);
-    const size_t llds = line_lds(M, T), flds = fwdinv_lds(M, T), clds = column_lds(N, KB);
-    const dim3 gl(N / T, (unsigned)planes), gc(L / KB, (unsigned)planes);
-    float2* twM = reinterpret_cast<float2*>(ws + Ly.twM);
-    float2* twN = reinterpret_cast<float2*>(ws + Ly.twN);
-    const float* Ct = reinterpret_cast<const float*>(ws + Ly.C);
-    const float* prm = reinterpret_cast<const float*>(ws + Ly.prm);
-    float2* spec0 = reinterpret_cast<float2*>(ws + Ly.spec0);
-    float2* spec1 = reinterpret_cast<float2*>(ws + Ly.spec1);
-    float* traj = rec ? reinterpret_cast<float*>(ws + Ly.traj) : nullptr;
-    float* sbuf[2] = {rec ? nullptr : reinterpret_cast<float*>(ws + Ly.sA), rec ? nullptr : reinterpret_cast<float*>(ws + Ly.sbA)};
-    // H^T y = y (no PSF) in the spectral domain, as run_forward's 2-pass kernels: Y_h = F y per grid plane (the
-    // hln slot, unused by the 2-pass grid), added by every column pass; iteration 1 transforms a zero spectrum
-    float2* yh = reinterpret_cast<float2*>(ws + Ly.hln);
-    int rc = ln.run(ADMM_K_PREP, [&] { return launch_line_fwd(L, T, gl, flds, s, y, spec0, twM, N, br, kMapIn); });
-    if (rc) return rc;
-    rc = ln.run(ADMM_K_PREP, [&] {
-        return launch_column(N, 5, gc, clds, s, spec0, spec1, Ct, nullptr, twN, L, KB, 1.0f, nullptr, nullptr, br, yh);
-    });
-    if (rc) return rc;
-    if (hipMemsetAsync(spec0, 0, planes * MN * 4, s) != hipSuccess) return fail(ADMM_E_HIP, "hipMemsetAsync");
-    for (int it = 1; it <= maxit; ++it) {
-        rc = ln.run(ADMM_K_COLUMN, [&] {
-            return launch_column(N, 6, gc, clds, s, spec0, spec1, Ct, nullptr, twN, L, KB, 1.0f, nullptr, nullptr, br, yh);
-        });
-        if (rc) return rc;
-        if (it == maxit) {
-            rc = ln.run(ADMM_K_FINAL, [&] { return launch_line_inv(L, T, gl, flds, s, spec1, x_out, twM, N, br, kMapOut); });
-            if (rc) return rc;
-            break;
-        }
-        // recording: s_it into slot it - 1 (the first iteration reads no s); otherwise the two s buffers in turn
-        float* sn = rec ? traj + (size_t)(it - 1) * sstride : ((it & 1) ? sbuf[0] : sbuf[1]);
-        const float* so = rec ? (it >= 2 ? traj + (size_t)(it - 2) * sstride : sn) : ((it & 1) ? sbuf[1] : sbuf[0]);
-        rc = ln.run(ADMM_K_LINE, [&] {
-            return launch_line(L, T, gl, llds, s, spec1, spec0, so, sn, nullptr, twM, N, prm, it == 1 ? 1 : 0, kThreads, br);
-        });
-        if (rc) return rc;
-    }
-    return ADMM_OK;
-}
-
-int run_multi_2pass_bwd(Launcher& ln, const float* x_bar, float* y_bar, float* lambda_bar, float* rho_bar,
-                        const float* x_out, int P, int B, int nbr, int K, unsigned char* ws, size_t planes,
-                        const MultiLayout& Ly) {
-    hipStream_t s = ln.s;
-    constexpr int M = kMultiM, N = kMultiN, L = M / 2;
-    const size_t MN = (size_t)M * N, ppb = (size_t)P * B, sstride = planes * 2 * MN;
-    const Branches br = multi2_branches(P, B, nbr);
-    const int T = bwd_line_T(M, N, false), KB = column_KB(M, N);
-    const size_t alds = line_lds(M, T) + 8 * 16, flds = fwdinv_lds(M, T), clds = column_lds(N, KB);
-    const dim3 gl(N / T, (unsigned)planes), gc(L / KB, (unsigned)planes);
-    float2* twM = reinterpret_cast<float2*>(ws + Ly.twM);
-    float2* twN = reinterpret_cast<float2*>(ws + Ly.twN);
-    const float* Ct = reinterpret_cast<const float*>(ws + Ly.C);
-    const float* prm = reinterpret_cast<const float*>(ws + Ly.prm);
-    float2* specA = reinterpret_cast<float2*>(ws + Ly.spec0);
-    float2* specB = reinterpret_cast<float2*>(ws + Ly.spec1);
-    const float* traj = reinterpret_cast<const float*>(ws + Ly.traj);
-    float* sb[2] = {reinterpret_cast<float*>(ws + Ly.sbA), reinterpret_cast<float*>(ws + Ly.sbB)};
-    float* vsum = y_bar ? reinterpret_cast<float*>(ws + Ly.vsum) : nullptr;
-    double* part = reinterpret_cast<double*>(ws + Ly.part);
-    hipError_t e = vsum ? hipMemsetAsync(vsum, 0, planes * MN * 4, s) : hipSuccess;
-    if (e != hipSuccess) return fail(ADMM_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-    int rc = ln.run(ADMM_K_PREP, [&] { return launch_line_fwd(L, T, gl, flds, s, x_bar, specA, twM, N, br, kMapOut); });
-    if (rc) return rc;
-    for (int k = K; k >= 1; --k) {
-        rc = ln.run(ADMM_K_COLUMN, [&] {
-            return launch_column(N, 0, gc, clds, s, specA, specB, Ct, nullptr, twN, L, KB, 1.0f, nullptr, nullptr, br);
-        });
-        if (rc) return rc;
-        const float* sk1 = k >= 2 ? traj + (size_t)(k - 2) * sstride : nullptr;
-        const float* skk = k < K ? traj + (size_t)(k - 1) * sstride : nullptr;
-        const float* sbi = k < K ? sb[k & 1] : nullptr;
-        float* sbo = sb[(k & 1) ^ 1];
-        double* rp = part + (size_t)(K - k) * Ly.rows_b * 2;
-        rc = ln.run(ADMM_K_ADJ, [&] {
-            return launch_line_adj(L, T, gl, alds, s, specB, sk1, rho_bar ? skk : nullptr, rho_bar ? x_out : nullptr, sbi,
-                                   sbo, vsum, specA, rp, twM, N, prm, k == 1 ? 1 : 0, k == K ? 1 : 0, false, br, Ly.pbs);
-        });
-        if (rc) return rc;
-    }
-    double* rt = reinterpret_cast<double*>(ws + Ly.rt);
-    for (int i = 0; i < nbr; ++i) {
-        rc = ln.run(ADMM_K_FINAL, [&] {
-            launch_reduce_cols(s, part + (size_t)i * Ly.pbs, rt + 2 * i, K * Ly.rows_b, 2,
-                               reinterpret_cast<double*>(ws + Ly.rtmp));
-        });
-        if (rc) return rc;
-        rc = ln.run(ADMM_K_FINAL, [&] {
-            hipLaunchKernelGGL(admm::grads_final_kernel, dim3(1), dim3(64), 0, s, rt + 2 * i, (const double*)nullptr,
-                               (const double*)nullptr, 0, prm + 4 * i, lambda_bar ? lambda_bar + i : nullptr,
-                               rho_bar ? rho_bar + i : nullptr, (float*)nullptr);
-        });
-        if (rc) return rc;
-    }
-    if (y_bar) {
-        rc = ln.run(ADMM_K_FINAL, [&] {
-            hipLaunchKernelGGL(admm::branch_sum_kernel, dim3(1024), dim3(kThreads), 0, s, vsum, y_bar, ppb * MN, nbr);
-        });
-        if (rc) return rc;
-    }
-    return ADMM_OK;
-}
-
+// ---- several branches in one grid ----------------------------------------------------------------------------
 int launch_forward_multi(const float* y, float* x_out, int M, int N, int P, int B, int nbr, const float* const* lambda,
                          const float* const* rho, int maxit, int flags, void* workspace, void* stream, size_t planes,
                          const MultiLayout& L) {
@@ -1313,19 +1238,17 @@ int launch_forward_multi(const float* y, float* x_out, int M, int N, int P, int 
     unsigned char* ws = static_cast<unsigned char*>(workspace);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     Launcher ln{s, g_prof.on, {}};
-    float* prm = reinterpret_cast<float*>(ws + L.prm);
-    float2* twM = reinterpret_cast<float2*>(ws + L.twM);
-    float2* twN = reinterpret_cast<float2*>(ws + L.twN);
+    const MultiView v = view(ws, L);
     for (int i = 0; i < nbr; ++i) {
-        float* Ct = reinterpret_cast<float*>(ws + L.C + (size_t)i * multi_C_bytes());
+        float* Ct = at<float>(ws, L.C + (size_t)i * multi_C_bytes());
         void* F = ws + L.F + (size_t)i * multi_F_bytes();
         const admm::ScalarSrc sc{lambda[i], rho[i], 0.f, 0.f};
         rc = ln.run(ADMM_K_SETUP, [&] {
             const size_t lds = (size_t)(M + N) * 16;
             const int nb = (int)(((size_t)(M / 2 + 1) * N + kThreads - 1) / kThreads);
             set_lds(admm::setup_kernel, lds);
-            hipLaunchKernelGGL(admm::setup_kernel, dim3(nb < 1024 ? nb : 1024), dim3(kThreads), lds, s, twM, twN, Ct,
-                               (float2*)nullptr, (const float*)nullptr, 0, 0, M, N, sc, prm + 4 * i, (double2*)nullptr);
+            hipLaunchKernelGGL(admm::setup_kernel, dim3(nb < 1024 ? nb : 1024), dim3(kThreads), lds, s, v.twM, v.twN, Ct,
+                               (float2*)nullptr, (const float*)nullptr, 0, 0, M, N, sc, v.prm + 4 * i, (double2*)nullptr);
         });
         if (rc) return rc;
         if (L.two_pass) continue;   // the 2-pass kernels read Ct itself
@@ -1337,43 +1260,35 @@ int launch_forward_multi(const float* y, float* x_out, int M, int N, int P, int 
         if (e != hipSuccess) return fail(ADMM_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
         return ln.finish();
     }
+    const bool iso = (flags & ADMM_MULTI_ISO) != 0;
     const bool rec = (flags & ADMM_MULTI_RECORD) != 0, masks = rec && (flags & ADMM_REC_MASKS) != 0;
     if (L.two_pass) {
-        rc = (flags & ADMM_MULTI_ISO) ? run_multi_2pass_iso_fwd(ln, y, x_out, P, B, nbr, maxit, rec, ws, planes, L)
-                                      : run_multi_2pass_fwd(ln, y, x_out, P, B, nbr, maxit, rec, ws, planes, L);
+        // recording: s_it into slot it - 1 of traj, |s_it| (per branch) into slot it - 1 of nrm; otherwise the s
+        // buffers sA / sbA in turn (isotropic: sA in place)
+        Traj tr;
+        tr.s = rec ? reinterpret_cast<float*>(v.traj) : nullptr;
+        tr.nrm = rec && iso ? v.nrm : nullptr;
+        float* sA = rec ? nullptr : at<float>(ws, L.sA);
+        rc = two_pass_forward(two_pass_multi(ln, P, B, nbr, planes, line_T(M, N), ws, L), y, x_out, maxit, iso, tr, sA,
+                              rec || iso ? sA : at<float>(ws, L.sbA));
         if (rc) return rc;
         return ln.finish();
     }
     const admm::plane::Branches br = multi_branches(P, B, nbr);
-    if (flags & ADMM_MULTI_ISO) {
-        // isotropic: per iteration one plane256_iso_kernel over every branch's planes and one iso_norm_kernel
-        // (each branch's batch norm over its own planes); recording: s_{k+1} into slot k, |s_{k+1}| too
-        namespace pk = admm::plane;
+    if (iso) {
+        // each branch's batch norm over its own planes; recording: s_{k+1} into slot k, |s_{k+1}| too
         const size_t kE = (size_t)M * N / 2;
-        float4* st = reinterpret_cast<float4*>(ws + (rec ? L.traj : L.sln));
-        const size_t tslot = rec ? planes * kE : 0;
-        float2* fl = reinterpret_cast<float2*>(ws + L.fmap);
-        float2* ql = reinterpret_cast<float2*>(ws + L.qpart);
-        for (int k = 0; k < maxit; ++k) {
-            rc = ln.run(ADMM_K_PLANE, [&] {
-                return pk::launch_plane_iso(y, x_out, ws + L.F, false, reinterpret_cast<float2*>(ws + L.hln),
-                                            st + (k > 0 ? (size_t)(k - 1) * tslot : 0), st + (size_t)k * tslot, fl, ql,
-                                            prm, k, maxit, planes, s, &br);
-            });
-            if (rc) return rc;
-            if (k + 1 < maxit) {
-                float2* nr = rec ? reinterpret_cast<float2*>(ws + L.nrm) + (size_t)k * nbr * kE : nullptr;
-                rc = ln.run(ADMM_K_NORM, [&] { return pk::launch_iso_norm(ql, fl, nr, prm, planes, s, &br); });
-                if (rc) return rc;
-            }
-        }
+        const FusedIso f{ws + L.F, v.prm, planes, &br, reinterpret_cast<float4*>(rec ? v.traj : v.sln),
+                         rec ? planes * kE : 0, rec ? reinterpret_cast<float2*>(v.nrm) : nullptr, nbr * kE,
+                         reinterpret_cast<float2*>(v.fmap), reinterpret_cast<float2*>(v.qpart)};
+        rc = fused_iso_forward(ln, f, y, x_out, false, v.hln, maxit);
+        if (rc) return rc;
         return ln.finish();
     }
     rc = ln.run(ADMM_K_PLANE, [&] {
-        return admm::plane::launch_plane(y, x_out, ws + L.F, false, reinterpret_cast<float2*>(ws + L.hln),
-                                         reinterpret_cast<float4*>(ws + L.sln), prm, maxit, planes, s,
-                                         rec && !masks ? reinterpret_cast<float4*>(ws + L.traj) : nullptr, &br,
-                                         masks ? reinterpret_cast<unsigned*>(ws + L.traj) : nullptr);
+        return admm::plane::launch_plane(y, x_out, ws + L.F, false, v.hln, reinterpret_cast<float4*>(v.sln), v.prm, maxit,
+                                         planes, s, rec && !masks ? reinterpret_cast<float4*>(v.traj) : nullptr, &br,
+                                         masks ? reinterpret_cast<unsigned*>(v.traj) : nullptr);
     });
     if (rc) return rc;
     return ln.finish();
@@ -1386,108 +1301,53 @@ int launch_backward_multi(const float* x_bar, float* y_bar, float* lambda_bar, f
     unsigned char* ws = static_cast<unsigned char*>(workspace);
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     Launcher ln{s, g_prof.on, {}};
-    hipError_t e;
     const int K = maxit;
     if (K == 0) {
-        if (y_bar && (e = hipMemsetAsync(y_bar, 0, ppb * MN * 4, s)) != hipSuccess) return fail(ADMM_E_HIP, "memset");
-        if (lambda_bar && (e = hipMemsetAsync(lambda_bar, 0, (size_t)nbr * 4, s)) != hipSuccess) return fail(ADMM_E_HIP, "memset");
-        if (rho_bar && (e = hipMemsetAsync(rho_bar, 0, (size_t)nbr * 4, s)) != hipSuccess) return fail(ADMM_E_HIP, "memset");
+        if (y_bar) HIPCHK(hipMemsetAsync(y_bar, 0, ppb * MN * 4, s));
+        if (lambda_bar) HIPCHK(hipMemsetAsync(lambda_bar, 0, (size_t)nbr * 4, s));
+        if (rho_bar) HIPCHK(hipMemsetAsync(rho_bar, 0, (size_t)nbr * 4, s));
         return ln.finish();
     }
+    const MultiView v = view(ws, L);
+    const bool iso = (flags & ADMM_MULTI_ISO) != 0;
     if (L.two_pass) {
-        rc = (flags & ADMM_MULTI_ISO)
-                 ? run_multi_2pass_iso_bwd(ln, x_bar, y_bar, lambda_bar, P, B, nbr, K, ws, planes, L)
-                 : run_multi_2pass_bwd(ln, x_bar, y_bar, lambda_bar, rho_bar, x_out, P, B, nbr, K, ws, planes, L);
+        const SweepBufs b{reinterpret_cast<const float*>(v.traj), iso ? v.nrm : nullptr, nullptr, nullptr,
+                          {at<float>(ws, L.sbA), at<float>(ws, L.sbB)}, y_bar ? at<float>(ws, L.vsum) : nullptr,
+                          at<float>(ws, L.wbar), v.rmap, at<float>(ws, L.Rpart), v.part, rho_bar ? x_out : nullptr};
+        // k = 1 launches no ISO_ADJ_R: its partial rows must read as zero
+        if (iso) HIPCHK(hipMemsetAsync(v.part, 0, (size_t)nbr * L.pbs * 8, s));
+        if (b.vsum) HIPCHK(hipMemsetAsync(b.vsum, 0, planes * MN * 4, s));
+        rc = two_pass_reverse(two_pass_multi(ln, P, B, nbr, planes, bwd_line_T(M, N, iso), ws, L), b, x_bar, K, iso, false);
+        if (rc) return rc;
+        rc = branch_grads(ln, v, L.pbs, K * L.rows_b, lambda_bar, rho_bar, b.vsum, y_bar, ppb * MN, nbr);
         if (rc) return rc;
         return ln.finish();
     }
     const admm::plane::Branches br = multi_branches(P, B, nbr);
-    const float* prm = reinterpret_cast<const float*>(ws + L.prm);
-    const bool masks = (flags & ADMM_REC_MASKS) != 0;
-    if (flags & ADMM_MULTI_ISO) {
-        // isotropic fused sweep over every branch's planes (plane_iso.hip): per reverse step one
-        // plane256_isoadj_kernel and one iso_radj_kernel; vbar in the forward's dead s state, Vsum lane-native
-        // in vsl and natural (per grid plane) in the H^T y slots, R partials in the q partial slots
-        namespace pk = admm::plane;
+    // each branch's Vsum in the natural layout (per grid plane): the forward's H^T y copies are dead
+    float* vout = y_bar ? reinterpret_cast<float*>(v.hln) : nullptr;
+    if (iso) {
+        // vbar in the forward's dead s state, Vsum lane-native in vsl, R partials in the q partial slots
         const size_t kE = MN / 2, rows = multi_iso_rows(K);
-        float4* trs = reinterpret_cast<float4*>(ws + L.traj);
-        const float2* trn = reinterpret_cast<const float2*>(ws + L.nrm);
-        float2* vb = reinterpret_cast<float2*>(ws + L.sln);
-        float2* rmap = reinterpret_cast<float2*>(ws + L.rmap);
-        float2* rpl = reinterpret_cast<float2*>(ws + L.qpart);
-        float* vout = y_bar ? reinterpret_cast<float*>(ws + L.hln) : nullptr;
-        double* part = reinterpret_cast<double*>(ws + L.part);
-        if ((e = hipMemsetAsync(part, 0, (size_t)nbr * rows * 16, s)) != hipSuccess) return fail(ADMM_E_HIP, "memset");
-        for (int k = K; k >= 1; --k) {
-            rc = ln.run(ADMM_K_ADJ, [&] {
-                return pk::launch_plane_isoadj(x_bar, ws + L.F, trs, planes * kE, trn, nbr * kE, vb,
-                                               reinterpret_cast<float4*>(ws + L.sbar), rmap, rpl,
-                                               reinterpret_cast<float2*>(ws + L.vsl), vout, prm, k, K, planes, s, &br);
-            });
-            if (rc) return rc;
-            if (k >= 2) {
-                rc = ln.run(ADMM_K_NORM, [&] {
-                    return pk::launch_iso_radj(rpl, rmap, trn + (size_t)(k - 2) * nbr * kE,
-                                               part + (size_t)(K - k) * 512 * 2, rows * 2, prm, planes, s, &br);
-                });
-                if (rc) return rc;
-            }
-        }
-        double* rt = reinterpret_cast<double*>(ws + L.rt);
-        for (int i = 0; i < nbr; ++i) {
-            rc = ln.run(ADMM_K_FINAL, [&] {
-                launch_reduce_cols(s, part + (size_t)i * rows * 2, rt + 2 * i, (int)rows, 2,
-                                   reinterpret_cast<double*>(ws + L.rtmp));
-            });
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_FINAL, [&] {
-                hipLaunchKernelGGL(admm::grads_final_kernel, dim3(1), dim3(64), 0, s, rt + 2 * i, (const double*)nullptr,
-                                   (const double*)nullptr, 0, prm + 4 * i, lambda_bar ? lambda_bar + i : nullptr,
-                                   (float*)nullptr, (float*)nullptr);
-            });
-            if (rc) return rc;
-        }
-        if (y_bar) {
-            rc = ln.run(ADMM_K_FINAL, [&] {
-                hipLaunchKernelGGL(admm::branch_sum_kernel, dim3(1024), dim3(kThreads), 0, s, vout, y_bar, ppb * MN, nbr);
-            });
-            if (rc) return rc;
-        }
+        HIPCHK(hipMemsetAsync(v.part, 0, (size_t)nbr * rows * 16, s));
+        const FusedIso f{ws + L.F, v.prm, planes, &br, reinterpret_cast<float4*>(v.traj), planes * kE,
+                         reinterpret_cast<float2*>(v.nrm), nbr * kE, nullptr, reinterpret_cast<float2*>(v.qpart)};
+        rc = fused_iso_reverse(ln, f, x_bar, reinterpret_cast<float2*>(v.sln), reinterpret_cast<float4*>(v.sbar),
+                               reinterpret_cast<float2*>(v.rmap), reinterpret_cast<float2*>(v.vsl), vout, v.part, rows * 2, K);
+        if (rc) return rc;
+        rc = branch_grads(ln, v, rows * 2, (int)rows, lambda_bar, rho_bar, vout, y_bar, ppb * MN, nbr);
+        if (rc) return rc;
         return ln.finish();
     }
-    float4* dxK = rho_bar ? reinterpret_cast<float4*>(ws + L.sln) : nullptr;   // the forward's s state is dead
-    float* vbuf = y_bar ? reinterpret_cast<float*>(ws + L.hln) : nullptr;     // ... and its H^T y copies
-    double* part = reinterpret_cast<double*>(ws + L.part);
-    if (dxK) {
-        rc = ln.run(ADMM_K_PREP, [&] { return admm::plane::launch_dx_lane(x_out, dxK, planes, s, &br); });
-        if (rc) return rc;
-    }
-    rc = ln.run(ADMM_K_ADJ, [&] {
-        return admm::plane::launch_plane_adj(x_bar, ws + L.F, ws + L.traj, dxK, reinterpret_cast<float4*>(ws + L.sbar),
-                                             reinterpret_cast<float2*>(ws + L.vsl), vbuf, part,
-                                             prm, K, planes, s, &br, masks);
-    });
+    // D x_K in the forward's s state, which is dead
+    rc = fused_reverse(ln, x_bar, ws + L.F, v.traj, (flags & ADMM_REC_MASKS) != 0, rho_bar ? x_out : nullptr,
+                       reinterpret_cast<float4*>(v.sln), reinterpret_cast<float4*>(v.sbar),
+                       reinterpret_cast<float2*>(v.vsl), vout, v.part, v.prm, K, planes, &br);
     if (rc) return rc;
-    double* rt = reinterpret_cast<double*>(ws + L.rt);
-    for (int i = 0; i < nbr; ++i) {
-        rc = ln.run(ADMM_K_FINAL, [&] {
-            launch_reduce_cols(s, part + 2 * (size_t)i * ppb, rt + 2 * i, (int)ppb, 2, reinterpret_cast<double*>(ws + L.rtmp));
-        });
-        if (rc) return rc;
-        rc = ln.run(ADMM_K_FINAL, [&] {
-            hipLaunchKernelGGL(admm::grads_final_kernel, dim3(1), dim3(64), 0, s, rt + 2 * i, (const double*)nullptr,
-                               (const double*)nullptr, 0, prm + 4 * i, lambda_bar ? lambda_bar + i : nullptr,
-                               rho_bar ? rho_bar + i : nullptr, (float*)nullptr);
-        });
-        if (rc) return rc;
-    }
-    if (y_bar) {
-        rc = ln.run(ADMM_K_FINAL, [&] {
-            hipLaunchKernelGGL(admm::branch_sum_kernel, dim3(1024), dim3(kThreads), 0, s, vbuf, y_bar, ppb * MN, nbr);
-        });
-        if (rc) return rc;
-    }
+    rc = branch_grads(ln, v, 2 * ppb, (int)ppb, lambda_bar, rho_bar, vout, y_bar, ppb * MN, nbr);
+    if (rc) return rc;
     return ln.finish();
 }
+#undef HIPCHK
 
 }  // namespace admm_capi

@@ -3,7 +3,7 @@
 //                   queries, the recordings registry, the profiler API, the output transport (copy / IPC)
 //   admm_paths.hip  the path decision table (plan_paths), the library options and the tile-size policy
 //   admm_launch.hip launch sequencing of the 2-pass / runtime-length / CU-resident / fused paths (the only TU
-//                   that includes the 2-pass kernels)
+//                   that includes the 2-pass kernels): one 2-pass forward and one reverse sweep for every caller
 // Reference interface: tvd_fft / tvd_fft_gpu, /root/reference/src/ops/ops.jl:99-188.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -236,6 +236,9 @@ struct GroupedLayout {
 GroupedLayout make_grouped_layout(int M, int N, size_t planes, int groups, bool psf, bool iso);
 
 // ---- launch sequencing (admm_launch.hip) ----
+// The four entry points below set a call up and pick its path; the 2-pass kernels' step sequences exist once
+// (two_pass_forward / two_pass_reverse on a TwoPass grid: a single or grouped solve, or the one-grid call's
+// branches), as do the isotropic norm step, the fused isotropic loops and the per-branch gradient assembly.
 // grp (run_forward): a grouped solve -- h holds one PSF per group, sc.lam / sc.rho point at nparam device values
 // (grp->prm_f = 0: one pair), lay is a GroupedLayout's; the setup kernels run over the groups
 // tables = false: the workspace already holds this call's twiddles, C / G tables and scalar block (a later plane

@@ -169,8 +169,8 @@ def test_multi_iso_is_the_branches(dev, n, B, P, K):
 @pytest.mark.parametrize("n,B,P,K", [(5, 2, 3, 12), (2, 1, 1, 1), (3, 3, 1, 2), (4, 5, 3, 6)])
 def test_multi_iso_2pass_is_the_branches(dev, n, B, P, K):
     """Below the plane-count rule (ADMM_OPT_MIN_PLANES at its default; 111 planes in all or fewer) the merged
-    isotropic grid runs the 2-pass kernels over every branch's planes (admm_launch.hip run_multi_2pass_iso_fwd /
-    _bwd, the reference's training configuration: 5 branches x batch 2 x RGB, train_cfg.json:10-14).  Each branch
+    isotropic grid runs the 2-pass kernels over every branch's planes (admm_launch.hip two_pass_forward /
+    two_pass_reverse on a two_pass_multi grid, the reference's training configuration: 5 branches x batch 2 x RGB, train_cfg.json:10-14).  Each branch
     alone is below the rule too, so it runs the same kernels: forward bitwise, lambda_bar to the fp64 order of its
     partial rows (the rows are laid out per branch), y_bar the branches' sum to rounding."""
     assert _lib.get_option("MIN_PLANES") == -1 and n * B * P < 112
