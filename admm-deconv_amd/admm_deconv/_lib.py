@@ -43,7 +43,10 @@ EXPORTS = ("admm_abi_version", "admm_last_error", "admm_tvd_workspace_bytes", "a
            "admm_tvd_multi_workspace_bytes", "admm_tvd_forward_multi_dev_f32",
            "admm_tvd_backward_multi_recorded_dev_f32", "admm_copy_async", "admm_query_paths", "admm_query_forward_schedule", "admm_clamp_backward_f32",
            "admm_path_name", "admm_ipc_get_handle", "admm_ipc_open", "admm_ipc_close",
-           "admm_tvd_grouped_workspace_bytes", "admm_tvd_forward_grouped_dev_f32", "admm_query_grouped_path")
+           "admm_tvd_grouped_workspace_bytes", "admm_tvd_forward_grouped_dev_f32", "admm_query_grouped_path",
+           "admm_tvd_grouped_backward_workspace_bytes", "admm_tvd_forward_grouped_record_dev_f32",
+           "admm_tvd_backward_grouped_recorded_dev_f32", "admm_tvd_backward_grouped_dev_f32",
+           "admm_query_grouped_paths")
 
 # record flags (the want_hbar word of the record entry points) and multi-branch flags
 REC_HBAR, REC_MASKS = 1, 2
@@ -177,6 +180,21 @@ def load():
                                                                                       c_void_p, c_size_t, c_void_p]
     L.admm_query_grouped_path.restype = c_int
     L.admm_query_grouped_path.argtypes = [c_int] * 4 + [ctypes.c_longlong, c_int, ctypes.POINTER(c_int)]
+    L.admm_tvd_grouped_backward_workspace_bytes.restype = c_int
+    L.admm_tvd_grouped_backward_workspace_bytes.argtypes = [c_int] * 11 + [ctypes.POINTER(c_size_t)]
+    # y, x_out, M, N, P, B, gb, gp, h, kh, kw, lambda, rho, nparam, iso, maxit, rec_flags, workspace, bytes, stream
+    L.admm_tvd_forward_grouped_record_dev_f32.restype = c_int
+    L.admm_tvd_forward_grouped_record_dev_f32.argtypes = [c_void_p, c_void_p] + [c_int] * 6 + [
+        c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]
+    # y, x_bar, y_bar, h_bar, lambda_bar, rho_bar, M, N, P, B, gb, gp, h, kh, kw, lambda, rho, nparam, iso, maxit,
+    # x_out, workspace, bytes, stream
+    L.admm_tvd_backward_grouped_recorded_dev_f32.restype = c_int
+    L.admm_tvd_backward_grouped_recorded_dev_f32.argtypes = [c_void_p] * 6 + [c_int] * 6 + [
+        c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]
+    L.admm_tvd_backward_grouped_dev_f32.restype = c_int
+    L.admm_tvd_backward_grouped_dev_f32.argtypes = list(L.admm_tvd_backward_grouped_recorded_dev_f32.argtypes)
+    L.admm_query_grouped_paths.restype = c_int
+    L.admm_query_grouped_paths.argtypes = [c_int] * 4 + [ctypes.c_longlong] + [c_int] * 5 + [ctypes.POINTER(c_int)] * 2
     L.admm_path_name.restype = ctypes.c_char_p
     L.admm_path_name.argtypes = [c_int]
     _lib = L
@@ -225,6 +243,24 @@ def query_grouped_path(M, N, iso=False, kh=0, planes=0, groups=1):
 
 
 MODE_FORWARD, MODE_RECORD, MODE_BACKWARD = 0, 1, 2
+
+
+def grouped_backward_workspace_bytes(M, N, P, B, gb, gp, kh, kw, iso, maxit, rec_flags=0):
+    """rec_flags: REC_HBAR when h_bar will be wanted (REC_MASKS is accepted and not honoured)."""
+    out = ctypes.c_size_t(0)
+    check(load().admm_tvd_grouped_backward_workspace_bytes(M, N, P, B, gb, gp, kh, kw, int(bool(iso)), int(maxit),
+                                                           int(rec_flags), ctypes.byref(out)))
+    return out.value
+
+
+def query_grouped_paths(M, N, iso=False, kh=0, planes=0, groups=1, mode=MODE_RECORD, flags=0, want_hbar=False,
+                        want_rho=False):
+    """admm_query_grouped_paths: (forward path name, reverse-sweep path name or None) of a grouped call."""
+    L = load()
+    f, b = ctypes.c_int(0), ctypes.c_int(0)
+    check(L.admm_query_grouped_paths(M, N, int(bool(iso)), kh, int(planes), int(groups), mode, int(flags),
+                                     int(want_hbar), int(want_rho), ctypes.byref(f), ctypes.byref(b)))
+    return L.admm_path_name(f.value).decode(), (L.admm_path_name(b.value).decode() if b.value else None)
 
 
 def query_paths(M, N, iso=False, kh=0, mode=MODE_FORWARD, flags=0, want_hbar=False, want_rho=False, planes=0):

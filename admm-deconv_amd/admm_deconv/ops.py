@@ -20,7 +20,9 @@ import torch
 from . import _lib
 
 __all__ = ["tvd_fft", "tvd_fft_backward", "tvd_fft_record", "tvd_fft_backward_recorded", "Recording", "Workspace",
-           "tvd_fft_multi", "tvd_fft_multi_backward_recorded", "multi_supported", "tvd_fft_grouped"]
+           "tvd_fft_multi", "tvd_fft_multi_backward_recorded", "multi_supported", "tvd_fft_grouped",
+           "tvd_fft_grouped_record", "tvd_fft_grouped_backward_recorded", "tvd_fft_grouped_backward", "tvd_fft_grouped_grad",
+           "GroupedRecording"]
 
 
 class Workspace:
@@ -462,14 +464,48 @@ def tvd_fft_grouped(y, lam, rho, h, isotropic=False, maxit=100, *, out=None, wor
          are refused: give B * P).
     lam, rho: floats, or tensors of 1 or gb * gp elements (group order b * gp + p); they stay on the device.
     isotropic: the batch coupling of the reference is kept over ALL planes, so lam and rho must have one element.
-    Forward only: the grouped adjoint does not exist yet."""
+    Not differentiable itself: tvd_fft_grouped_grad is the entry with the grouped adjoint."""
     if not isinstance(y, torch.Tensor) or y.device.type != "cuda" or y.dtype != torch.float32:
         raise TypeError("tvd_fft_grouped: y must be a float32 torch tensor on a ROCm device")
     if y.dim() != 4:
         raise ValueError("tvd_fft_grouped: y must be 4-D (B, P, N, M)")
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (y, h, lam, rho)):
-        raise NotImplementedError("tvd_fft_grouped is forward only: the grouped adjoint does not exist yet "
-                                  "(detach the inputs, or loop tvd_fft per group under autograd)")
+        raise NotImplementedError("tvd_fft_grouped is the plain forward: call tvd_fft_grouped_grad for the grouped "
+                                  "adjoint under autograd (or detach the inputs)")
+    y4, hbuf, lt, rt, nparam, gb, gp = _grouped_args(y, lam, rho, h)
+    B, P, N, M = y4.shape
+    kw, kh = (0, 0) if hbuf is None else hbuf.shape[2:]
+    hp = None if hbuf is None else hbuf.data_ptr()
+    if out is None:
+        out = torch.empty_like(y4)
+    elif out.shape != y4.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != y.device:
+        raise ValueError("out must be a contiguous float32 tensor of y's shape on y's device")
+    stream, s_handle = _stream_of(stream, y.device)
+    nbytes = _lib.grouped_workspace_bytes(M, N, P, B, gb, gp, kh, kw, isotropic)
+    if workspace is None:
+        workspace = _default_workspace("grouped", y.device, stream)
+    ws_ptr, ws_len = workspace.get(nbytes, y.device, stream)
+    _record_streams(stream, y.device, lt, rt, hbuf)
+    _lib.check(_lib.load().admm_tvd_forward_grouped_dev_f32(
+        y4.data_ptr(), out.data_ptr(), M, N, P, B, gb, gp, hp, kh, kw, lt.data_ptr(), rt.data_ptr(), nparam,
+        int(bool(isotropic)), int(maxit), ws_ptr, ws_len, s_handle))
+    return out
+
+
+def _record_streams(stream, device, *tensors):
+    if isinstance(stream, torch.cuda.Stream) and stream != torch.cuda.current_stream(device):
+        for t in tensors:
+            if t is not None:
+                t.record_stream(stream)
+
+
+def _grouped_args(y, lam, rho, h):
+    """A grouped call's arguments resolved: (y4, h (gb, gp, kw, kh) on the device or None, lambda and rho as device
+    tensors of nparam elements each, nparam, gb, gp).  Nothing is read back to the host."""
+    if not isinstance(y, torch.Tensor) or y.device.type != "cuda" or y.dtype != torch.float32:
+        raise TypeError("tvd_fft_grouped: y must be a float32 torch tensor on a ROCm device")
+    if y.dim() != 4:
+        raise ValueError("tvd_fft_grouped: y must be 4-D (B, P, N, M)")
     y4 = y.detach().contiguous()
     B, P, N, M = y4.shape
     if h is None:
@@ -496,7 +532,6 @@ def tvd_fft_grouped(y, lam, rho, h, isotropic=False, maxit=100, *, out=None, wor
         if gb not in (1, B) or gp not in (1, P):
             raise ValueError(f"tvd_fft_grouped: h's leading dims ({gb}, {gp}) must be (1 or B = {B}, 1 or P = {P})")
         hbuf = h.detach().to(device=y.device, dtype=torch.float32).contiguous()
-        hp = hbuf.data_ptr()
     G = gb * gp
     lt, rt = _group_params(lam, "lambda", G, y.device), _group_params(rho, "rho", G, y.device)
     nparam = max(lt.numel(), rt.numel())
@@ -504,23 +539,138 @@ def tvd_fft_grouped(y, lam, rho, h, isotropic=False, maxit=100, *, out=None, wor
         lt = lt.expand(nparam).contiguous()
     if rt.numel() != nparam:
         rt = rt.expand(nparam).contiguous()
-    if out is None:
-        out = torch.empty_like(y4)
-    elif out.shape != y4.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != y.device:
-        raise ValueError("out must be a contiguous float32 tensor of y's shape on y's device")
+    return y4, hbuf, lt, rt, nparam, gb, gp
+
+
+# ---- grouped adjoint (admm_tvd_backward_grouped_*, include/admm_deconv.h) ----
+class GroupedRecording:
+    """One grouped forward recorded for its adjoint (admm_tvd_forward_grouped_record_dev_f32); consumed by
+    tvd_fft_grouped_backward_recorded.  Memory as Recording, plus one table set per group."""
+
+    __slots__ = ("workspace", "y4", "hb", "lt", "rt", "nparam", "gb", "gp", "iso", "maxit", "want_h")
+
+
+def _grouped_call(fn, y4, xb, outs, hb, lt, rt, nparam, gb, gp, iso, maxit, x, ws_ptr, ws_len, s_handle):
+    B, P, N, M = y4.shape
+    kw, kh = (0, 0) if hb is None else hb.shape[2:]
+    _lib.check(fn(y4.data_ptr(), xb.data_ptr(), *[None if t is None else t.data_ptr() for t in outs], M, N, P, B, gb, gp,
+                  None if hb is None else hb.data_ptr(), kh, kw, lt.data_ptr(), rt.data_ptr(), nparam, int(iso), int(maxit),
+                  x.data_ptr(), ws_ptr, ws_len, s_handle))
+
+
+def _grouped_outs(y4, hb, nparam, want_h, need_y, need_rho):
+    y_bar = torch.empty_like(y4) if need_y else None
+    h_bar = torch.empty_like(hb) if want_h else None
+    lam_bar = torch.zeros(nparam, dtype=torch.float32, device=y4.device)
+    rho_bar = torch.zeros(nparam, dtype=torch.float32, device=y4.device) if need_rho else None
+    return y_bar, h_bar, lam_bar, rho_bar
+
+
+def tvd_fft_grouped_record(y, lam, rho, h, isotropic=False, maxit=100, *, need_h=True, stream=None):
+    """tvd_fft_grouped that records its trajectory.  Returns (x, GroupedRecording).  need_h: the replay will be asked
+    for h_bar (the dim-2 spectra are then recorded too, by the 2-pass forward)."""
+    y4, hb, lt, rt, nparam, gb, gp = _grouped_args(y, lam, rho, h)
+    B, P, N, M = y4.shape
+    kw, kh = (0, 0) if hb is None else hb.shape[2:]
     stream, s_handle = _stream_of(stream, y.device)
-    nbytes = _lib.grouped_workspace_bytes(M, N, P, B, gb, gp, kh, kw, isotropic)
+    rec = GroupedRecording()
+    rec.y4, rec.hb, rec.lt, rec.rt, rec.nparam, rec.gb, rec.gp = y4, hb, lt, rt, nparam, gb, gp
+    rec.iso, rec.maxit, rec.want_h = bool(isotropic), int(maxit), bool(need_h and hb is not None)
+    flags = _lib.REC_HBAR if rec.want_h else 0
+    nbytes = _lib.grouped_backward_workspace_bytes(M, N, P, B, gb, gp, kh, kw, isotropic, maxit, flags)
+    rec.workspace = Workspace()
+    ws_ptr, ws_len = rec.workspace.get(nbytes, y.device, stream)
+    _record_streams(stream, y.device, lt, rt, hb)
+    x = torch.empty_like(y4)
+    _lib.check(_lib.load().admm_tvd_forward_grouped_record_dev_f32(
+        y4.data_ptr(), x.data_ptr(), M, N, P, B, gb, gp, None if hb is None else hb.data_ptr(), kh, kw, lt.data_ptr(),
+        rt.data_ptr(), nparam, int(rec.iso), rec.maxit, flags, ws_ptr, ws_len, s_handle))
+    return x, rec
+
+
+def tvd_fft_grouped_backward_recorded(rec, x, x_bar, *, need_y=True, need_rho=True, stream=None):
+    """Reverse sweep of a recorded grouped forward (x = that forward's output, unmodified).  Returns
+    (y_bar, h_bar (gb, gp, kw, kh) or None, lam_bar (nparam,), rho_bar (nparam,) or None): one gradient per group's
+    PSF; entry g of lam_bar / rho_bar sums over group g's planes (nparam = 1: over all planes).  Consumes the
+    recording."""
+    if rec.workspace is None:
+        raise RuntimeError("recording already consumed")
+    y4 = rec.y4
+    xb = x_bar.reshape(y4.shape).to(torch.float32).contiguous()
+    x4 = x.reshape(y4.shape)
+    if not x4.is_contiguous():
+        raise ValueError("x must be the recorded forward's (contiguous) output")
+    stream, s_handle = _stream_of(stream, y4.device)
+    ws_ptr, ws_len = rec.workspace.get(0, y4.device, stream)
+    outs = _grouped_outs(y4, rec.hb, rec.nparam, rec.want_h, need_y, need_rho)
+    _record_streams(stream, y4.device, rec.lt, rec.rt, rec.hb)
+    _grouped_call(_lib.load().admm_tvd_backward_grouped_recorded_dev_f32, y4, xb, outs, rec.hb, rec.lt, rec.rt, rec.nparam,
+                  rec.gb, rec.gp, rec.iso, rec.maxit, x4, ws_ptr, ws_len, s_handle)
+    rec.workspace = None
+    return outs
+
+
+def tvd_fft_grouped_backward(y, x_bar, lam, rho, h, isotropic=False, maxit=100, *, need_h=True, need_y=True,
+                             need_rho=True, workspace=None, stream=None):
+    """The grouped forward and its adjoint in one call.  Returns (x, y_bar, h_bar, lam_bar, rho_bar), shaped as
+    tvd_fft_grouped_backward_recorded's."""
+    y4, hb, lt, rt, nparam, gb, gp = _grouped_args(y, lam, rho, h)
+    B, P, N, M = y4.shape
+    kw, kh = (0, 0) if hb is None else hb.shape[2:]
+    xb = x_bar.reshape(y4.shape).to(torch.float32).contiguous()
+    want_h = bool(need_h and hb is not None)
+    stream, s_handle = _stream_of(stream, y.device)
+    nbytes = _lib.grouped_backward_workspace_bytes(M, N, P, B, gb, gp, kh, kw, isotropic, maxit,
+                                                   _lib.REC_HBAR if want_h else 0)
     if workspace is None:
-        workspace = _default_workspace("grouped", y.device, stream)
+        workspace = _default_workspace("grouped_bwd", y.device, stream)
     ws_ptr, ws_len = workspace.get(nbytes, y.device, stream)
-    if isinstance(stream, torch.cuda.Stream) and stream != torch.cuda.current_stream(y.device):
-        for t in (lt, rt, hbuf):
-            if t is not None:
-                t.record_stream(stream)
-    _lib.check(_lib.load().admm_tvd_forward_grouped_dev_f32(
-        y4.data_ptr(), out.data_ptr(), M, N, P, B, gb, gp, hp, kh, kw, lt.data_ptr(), rt.data_ptr(), nparam,
-        int(bool(isotropic)), int(maxit), ws_ptr, ws_len, s_handle))
-    return out
+    x = torch.empty_like(y4)
+    outs = _grouped_outs(y4, hb, nparam, want_h, need_y, need_rho)
+    _record_streams(stream, y.device, lt, rt, hb)
+    _grouped_call(_lib.load().admm_tvd_backward_grouped_dev_f32, y4, xb, outs, hb, lt, rt, nparam, gb, gp, isotropic, maxit,
+                  x, ws_ptr, ws_len, s_handle)
+    return (x, *outs)
+
+
+class _TvdFFTGroupedFn(torch.autograd.Function):
+    """Differentiable tvd_fft_grouped: one recorded grouped forward, one reverse sweep."""
+
+    @staticmethod
+    def forward(ctx, y, lam_t, rho_t, h_t, isotropic, maxit):
+        has_h = h_t.numel() > 0
+        x, ctx.rec = tvd_fft_grouped_record(y, lam_t, rho_t, h_t if has_h else None, isotropic, maxit,
+                                            need_h=has_h and ctx.needs_input_grad[3])
+        ctx.save_for_backward(y, lam_t, rho_t, h_t, x)
+        return x
+
+    @staticmethod
+    def backward(ctx, x_bar):
+        _y, lam_t, rho_t, h_t, x = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        yb, hb, lb, rb = tvd_fft_grouped_backward_recorded(ctx.rec, x, x_bar, need_y=need[0], need_rho=need[2])
+        ctx.rec = None
+
+        def shaped(g, p):   # a 1-element parameter next to per-group ones gets the sum over the groups
+            if g.numel() != p.numel():
+                g = g.sum()
+            return g.reshape(p.shape).to(p.dtype)
+        return (yb if need[0] else None, shaped(lb, lam_t) if need[1] else None, shaped(rb, rho_t) if need[2] else None,
+                hb.reshape(h_t.shape).to(h_t.dtype) if ctx.needs_input_grad[3] and hb is not None else None, None, None)
+
+
+def tvd_fft_grouped_grad(y, lam, rho, h, isotropic=False, maxit=100):
+    """tvd_fft_grouped under autograd: when y, h, lam or rho requires grad, one recorded grouped forward and one
+    reverse sweep (the dim-2 spectra for h_bar are recorded only if h requires grad; rho_bar and y_bar are formed only
+    if wanted).  Gradients come back in the shapes given: h.grad (gb, gp, kw, kh); a 1-element lam next to per-group
+    rho gets the sum over the groups; a Python float gets none.  Without grad it is the plain call."""
+    ts = [t for t in (y, lam, rho, h) if isinstance(t, torch.Tensor)]
+    if not (torch.is_grad_enabled() and any(t.requires_grad for t in ts)):
+        return tvd_fft_grouped(y, lam, rho, h, isotropic, maxit)
+    dev = y.device
+    as_t = lambda v: v if isinstance(v, torch.Tensor) else torch.full((1,), float(v), device=dev)  # noqa: E731
+    h_t = h if h is not None else torch.empty(0, device=dev)
+    return _TvdFFTGroupedFn.apply(y, as_t(lam), as_t(rho), h_t, bool(isotropic), int(maxit))
 
 
 def multi_supported(y, isotropic=False, psf=None, group=None):

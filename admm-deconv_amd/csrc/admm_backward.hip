@@ -74,7 +74,8 @@ __device__ __forceinline__ void load_s_quad(const float* __restrict__ sp, int j,
     }
 }
 
-template <int L, int T, bool LN = false>
+// GRP: a grouped solve (br.nbr = 0): the plane's group scalars, partial rows by plane (pbs = 0)
+template <int L, int T, bool LN = false, bool GRP = false>
 __global__ __launch_bounds__(kThreads) void line_adj_kernel(const float2* __restrict__ spec1,
                                                             const float* __restrict__ sk1, const float* __restrict__ sk,
                                                             const float* __restrict__ xK,
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void line_adj_kernel(const float2* __rest
     const size_t MN = (size_t)M * N;
     const int tid = threadIdx.x;
     const size_t poff = (size_t)plane * 2 * MN;
-    const BranchOf bo = branch_of(br, plane);
+    const BranchOf bo = plane::plane_of<GRP>(br, plane);
     const float tau = prm[(size_t)bo.i * br.prm_f], rho = prm[(size_t)bo.i * br.prm_f + 1];   // (setup_kernel)
 
     for (int t = tid; t < M; t += kThreads) tw[t] = twM[t];
@@ -332,9 +333,9 @@ __global__ __launch_bounds__(kThreads) void reduce_cols_kernel(const double* __r
 
 // h_bar through A (needs Q): hbA[b][a] = -(1/MN) sum_{kj, k=0..L} w_k C^2 Q d|Sigma|^2/dh[b][a],
 // d|Sigma|^2/dh = 2 Re(conj(Sigma) e^{-2 pi i (a k/M + b kj/N)}); Sigma rebuilt in fp64.  One block per tap.
-__global__ __launch_bounds__(kThreads) void hbarA_kernel(const double* __restrict__ Q, const float* __restrict__ Ct,
-                                                         const double2* __restrict__ SigT, int kh, int M, int N,
-                                                         double* __restrict__ out) {
+__device__ __forceinline__ void hbarA_body(const double* __restrict__ Q, const float* __restrict__ Ct,
+                                           const double2* __restrict__ SigT, int kh, int M, int N,
+                                           double* __restrict__ out) {
     __shared__ double red[kThreads / 64];
     const int tap = blockIdx.x;
     const int b = tap / kh, a = tap - b * kh;
@@ -360,6 +361,11 @@ __global__ __launch_bounds__(kThreads) void hbarA_kernel(const double* __restric
         out[tap] = -sum / ((double)M * (double)N);
     }
 }
+__global__ __launch_bounds__(kThreads) void hbarA_kernel(const double* __restrict__ Q, const float* __restrict__ Ct,
+                                                         const double2* __restrict__ SigT, int kh, int M, int N,
+                                                         double* __restrict__ out) {
+    hbarA_body(Q, Ct, SigT, kh, M, N, out);
+}
 
 // Q[q] = sum over planes of Qp[p][q] (fixed order, fp64)
 __global__ void reduce_planes_kernel(const double* __restrict__ Qp, double* __restrict__ Q, int planes, int n) {
@@ -371,9 +377,12 @@ __global__ void reduce_planes_kernel(const double* __restrict__ Qp, double* __re
 }
 
 // Final assembly of the scalar / PSF gradients into the caller's fp32 outputs.
-__global__ void grads_final_kernel(const double* __restrict__ rt, const double* __restrict__ hb_corr,
-                                   const double* __restrict__ hb_A, int ntaps, const float* __restrict__ prm,
-                                   float* __restrict__ lam_bar, float* __restrict__ rho_bar, float* __restrict__ h_bar) {
+// scal: this call forms the scalar gradients (a grouped call with one (lambda, rho) pair: group 0 only)
+__device__ __forceinline__ void grads_final_body(const double* __restrict__ rt, const double* __restrict__ hb_corr,
+                                                 const double* __restrict__ hb_A, int ntaps,
+                                                 const float* __restrict__ prm, float* __restrict__ lam_bar,
+                                                 float* __restrict__ rho_bar, float* __restrict__ h_bar, bool scal) {
+    if (!scal) lam_bar = rho_bar = nullptr;
     const float lam = prm[2]; const float rho = prm[1];   // device-resident scalars (setup_kernel)
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t == 0) {
@@ -382,6 +391,11 @@ __global__ void grads_final_kernel(const double* __restrict__ rt, const double* 
         if (rho_bar) *rho_bar = (float)(rt[0] - tau_bar * lam / ((double)rho * rho));
     }
     if (h_bar && t < ntaps) h_bar[t] = (float)(hb_corr[t] + (hb_A ? hb_A[t] : 0.0));
+}
+__global__ void grads_final_kernel(const double* __restrict__ rt, const double* __restrict__ hb_corr,
+                                   const double* __restrict__ hb_A, int ntaps, const float* __restrict__ prm,
+                                   float* __restrict__ lam_bar, float* __restrict__ rho_bar, float* __restrict__ h_bar) {
+    grads_final_body(rt, hb_corr, hb_A, ntaps, prm, lam_bar, rho_bar, h_bar, true);
 }
 
 
@@ -689,6 +703,95 @@ __global__ __launch_bounds__(kThreads) void iso_adj_b_kernel(const float* __rest
         Z = F0;
     }
     pack_store<L>(Z, spec0 + (size_t)plane * N * L, j0, T, N, tw);
+}
+
+
+// ==============================================================================================
+// Grouped adjoint (admm_tvd_backward_grouped_*): gradient assembly per PSF / (lambda, rho) group.
+// The sweep leaves the same fp64 partial rows as a single solve -- (rho_bar, tau_bar) per (step, plane, line block),
+// h_bar correlation taps per (plane, line tile), Q accumulators per plane -- and these kernels sum each group's
+// rows in a fixed order (no atomics), then assemble per group.  A group's planes may be strided (per-channel
+// groups: gb = 1, gp = P), so they are enumerated from the descriptor.  Defined last in this file.
+// ==============================================================================================
+// planes per group / the j-th plane of group g of a grouped descriptor (plane_api.hpp Branches, nbr = 0)
+__host__ __device__ inline int group_planes(const Branches& br) {
+    return (br.gmul_b ? 1 : br.ppb / br.P) * (br.gmul_p ? 1 : br.P);
+}
+__host__ __device__ inline int group_plane(const Branches& br, int g, int j) {
+    const int b0 = br.gmul_b ? g / br.gmul_b : 0;            // the group's image (per-image groups)
+    const int p0 = br.gmul_p ? g - b0 * br.gmul_b : 0;       // the group's channel (per-channel groups)
+    if (br.gmul_p) return (br.gmul_b ? b0 : j) * br.P + p0;
+    return br.gmul_b ? b0 * br.P + j : j;
+}
+
+// part: rows [step][plane][blk] of w doubles (step_rows rows per step).  Block (c, g, sp) sums column c over part sp
+// of group g's nsteps x planes x nblk rows into out[(g nsplit + sp) w + c]: nsplit = 1 writes the group sums, else
+// reduce_groups_fin_kernel sums the nsplit partials (fixed partition: deterministic).
+__global__ __launch_bounds__(kThreads) void reduce_groups_kernel(const double* __restrict__ part,
+                                                                 double* __restrict__ out, int nsteps, size_t step_rows,
+                                                                 int nblk, int w, Branches br) {
+    __shared__ double red[kThreads];
+    const int c = blockIdx.x, g = blockIdx.y, sp = blockIdx.z, nsplit = gridDim.z;
+    const int per = group_planes(br) * nblk;
+    const long long n = (long long)nsteps * per;
+    const long long chunk = (n + nsplit - 1) / nsplit;
+    const long long i0 = sp * chunk, i1 = i0 + chunk < n ? i0 + chunk : n;
+    double s = 0.0;
+    for (long long i = i0 + threadIdx.x; i < i1; i += blockDim.x) {
+        const int st = (int)(i / per), r = (int)(i - (long long)st * per);
+        const int j = r / nblk, blk = r - j * nblk;
+        const size_t row = (size_t)st * step_rows + (size_t)group_plane(br, g, j) * nblk + blk;
+        s += part[row * w + c];
+    }
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = blockDim.x / 2; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[((size_t)g * nsplit + sp) * w + c] = red[0];
+}
+
+// out[g w + c] = sum over the nsplit partials of group g (one thread per (g, c), fixed order)
+__global__ void reduce_groups_fin_kernel(const double* __restrict__ tmp, double* __restrict__ out, int nsplit, int w,
+                                         int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;   // g w + c
+    if (i >= n) return;
+    const int g = i / w, c = i - g * w;
+    double s = 0.0;
+    for (int sp = 0; sp < nsplit; ++sp) s += tmp[((size_t)g * nsplit + sp) * w + c];
+    out[i] = s;
+}
+
+// Q[g][q] = sum over group g's planes of Qp[plane][q] (fixed order, fp64); grid (blocks over q, groups)
+__global__ void reduce_planes_grouped_kernel(const double* __restrict__ Qp, double* __restrict__ Q, int n, Branches br) {
+    const int g = blockIdx.y, np = group_planes(br);
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < n; q += gridDim.x * blockDim.x) {
+        double s = 0.0;
+        for (int j = 0; j < np; ++j) s += Qp[(size_t)group_plane(br, g, j) * n + q];
+        Q[(size_t)g * n + q] = s;
+    }
+}
+
+// hbarA_kernel per group (grid y = group): its Q, its C table (tab_f floats apart) and its PSF spectrum
+__global__ __launch_bounds__(kThreads) void hbarA_grouped_kernel(const double* __restrict__ Q, const float* __restrict__ Ct,
+                                                                 const double2* __restrict__ SigT, int kh, int ntaps, int M,
+                                                                 int N, double* __restrict__ out, unsigned tab_f) {
+    const size_t g = blockIdx.y, nq = (size_t)(M / 2 + 1) * N;
+    hbarA_body(Q + g * nq, Ct + g * tab_f, SigT + g * nq, kh, M, N, out + g * ntaps);
+}
+
+// grads_final_kernel per group (grid y = group): h_bar[g] always; lambda_bar[g], rho_bar[g] from the group's sums and
+// scalar block for g < nparam (one pair for every group: nparam = 1, rt holds the sums over all planes)
+__global__ void grads_final_grouped_kernel(const double* __restrict__ rt, const double* __restrict__ hb_corr,
+                                           const double* __restrict__ hb_A, int ntaps, const float* __restrict__ prm,
+                                           unsigned prm_f, int nparam, float* __restrict__ lam_bar,
+                                           float* __restrict__ rho_bar, float* __restrict__ h_bar) {
+    const size_t g = blockIdx.y;
+    const bool scal = (int)g < nparam;
+    grads_final_body(rt + (scal ? 2 * g : 0), hb_corr ? hb_corr + g * ntaps : nullptr, hb_A ? hb_A + g * ntaps : nullptr,
+                     ntaps, prm + g * prm_f, lam_bar ? lam_bar + g : nullptr, rho_bar ? rho_bar + g : nullptr,
+                     h_bar ? h_bar + g * ntaps : nullptr, scal);
 }
 
 }  // namespace admm

@@ -184,6 +184,7 @@ struct RecTag {
     int nbr;     // branches of a multi-branch recording (1: a single solve)
     int sharded; // recorded with a batch reducer: sharded calls plan without the plane-count rule, so a replay
                  // with (or without) one must match or it could plan another sweep than the trajectory's layout
+    int grouped, gb, gp, nparam;   // a grouped recording (admm_tvd_forward_grouped_record_dev_f32) and its grouping
     bool operator==(const RecTag& o) const { return std::memcmp(this, &o, sizeof(RecTag)) == 0; }
 };
 std::mutex g_rec_mu;
@@ -370,6 +371,96 @@ int forward_grouped(const float* y, float* x_out, int M, int N, int P, int B, in
                      static_cast<unsigned char*>(workspace), L.f, Traj{}, nullptr, path, true, &br);
     const int rc2 = ln.finish();
     return rc ? rc : rc2;
+}
+
+GroupedBwdLayout make_grouped_bwd_layout(int M, int N, int P, int B, int gb, int gp, int nparam, int kh, int kw, int maxit,
+                                         bool want_h, bool iso) {
+    GroupedBwdLayout L{};
+    const size_t planes = (size_t)P * B, G = (size_t)gb * gp, ntaps = (size_t)kh * kw;
+    const bool psf = kh > 0, hq = want_h && psf;
+    L.b = make_bwd_layout(M, N, planes, kh, kw, maxit, want_h, iso);
+    size_t off = align_up(L.b.total);
+    auto take = [&](size_t bytes) {
+        size_t o = off;
+        off = align_up(off + bytes);
+        return o;
+    };
+    // the grouped table blocks, as make_grouped_layout places them
+    L.tab_f = (unsigned)(align_up((size_t)(M / 2 + 1) * N * 4) / 4);
+    L.b.f.prm = take(G * 16);
+    L.b.f.C = take(G * L.tab_f * 4);
+    L.b.f.G = psf ? take(G * L.tab_f * 8) : 0;
+    L.b.f.F = fused_tables_shape(M, N) ? take(G * admm::plane::grouped_tables_bytes()) : 0;
+    // per group: PSF spectrum, Q, the two h_bar terms, the (rho_bar, tau_bar) sums
+    const size_t nq = (size_t)(M / 2 + 1) * N;
+    L.b.sig = hq ? take(G * nq * 16) : 0;
+    L.b.Q = hq ? take(G * nq * 8) : 0;
+    L.b.hcorr = psf ? take(G * ntaps * 8) : 0;
+    L.b.hA = hq ? take(G * ntaps * 8) : 0;
+    L.b.rt = take(G * 2 * 8);
+    // parts of the group-segmented sums: one (lambda, rho) pair sums every plane's rows, G pairs a group's
+    const int K = maxit < 1 ? 1 : maxit;
+    const size_t ppg = planes / G;
+    L.split_rt = iso ? 1 : group_split((long long)K * (L.b.nblk_line / (long long)planes) * (nparam > 1 ? ppg : planes));
+    L.split_h = psf ? group_split((long long)(N / L.b.TY) * ppg) : 1;
+    const size_t t_rt = (size_t)nparam * L.split_rt * 2, t_h = G * L.split_h * ntaps;
+    L.gtmp = take((t_rt > t_h ? t_rt : t_h) * 8);
+    L.total = L.b.total = off;
+    return L;
+}
+
+// The grouped adjoint: phases as run_backward (1 = record, 2 = replay, 3 = both).  Grouping, layouts and validation
+// are the grouped forward's (check_grouped); there is no reducer form.  ADMM_REC_MASKS is accepted and not honoured:
+// the full trajectory is recorded, so rho_bar stays available.
+int run_backward_grouped(int phases, int rec_flags, const float* y, const float* x_bar, float* y_bar, float* h_bar,
+                         float* lambda_bar, float* rho_bar, int M, int N, int P, int B, int gb, int gp, const float* h,
+                         int kh, int kw, const float* lambda, const float* rho, int nparam, int iso, int maxit,
+                         float* x_out, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_grouped(M, N, P, B, gb, gp, kh, kw, iso);
+    if (rc) return rc;
+    const int G = gb * gp;
+    if (kh > 0 && !h) return fail(ADMM_E_INVALID, "grouped adjoint: h is NULL with a %d x %d PSF", kh, kw);
+    if (!lambda || !rho) return fail(ADMM_E_INVALID, "grouped adjoint: lambda and rho must be device pointers");
+    if (nparam != 1 && nparam != G)
+        return fail(ADMM_E_INVALID, "grouped adjoint: nparam must be 1 or the group count %d (got %d)", G, nparam);
+    if (iso && nparam > 1)
+        return fail(ADMM_E_UNSUPPORTED, "grouped adjoint: the isotropic prox is one BT factor map per batch, so it takes "
+                                        "one (lambda, rho) pair (nparam = 1), got %d", nparam);
+    if (rec_flags & ~(ADMM_REC_HBAR | ADMM_REC_MASKS)) return fail(ADMM_E_INVALID, "grouped adjoint: unknown rec_flags 0x%x", rec_flags);
+    rc = check_common(y, x_out, maxit);
+    if (rc) return rc;
+    if ((phases & 2) && (reinterpret_cast<uintptr_t>(y_bar) & 15))
+        return fail(ADMM_E_INVALID, "y_bar must be a 16-byte aligned device pointer (or NULL: not needed)");
+    if ((phases & 2) && (!x_bar || (reinterpret_cast<uintptr_t>(x_bar) & 15)))
+        return fail(ADMM_E_INVALID, "x_bar must be a 16-byte aligned device pointer");
+    const size_t planes = (size_t)P * B;
+    const bool want_h = phases == 1 ? (rec_flags & ADMM_REC_HBAR) != 0 : h_bar != nullptr;
+    const GroupedPlan plan = plan_grouped_adjoint(M, N, iso != 0, kh > 0, planes, want_h);
+    const GroupedBwdLayout gl = make_grouped_bwd_layout(M, N, P, B, gb, gp, nparam, kh, kw, maxit, plan.want_h, iso != 0);
+    rc = check_ws(workspace, workspace_bytes, gl.total);
+    if (rc) return rc;
+    RecTag tag = make_tag(M, N, P, B, kh, kw, iso, maxit, plan.want_h, admm::ScalarSrc{lambda, rho, 0.f, 0.f});
+    tag.grouped = 1, tag.gb = gb, tag.gp = gp, tag.nparam = nparam;
+    {
+        std::lock_guard<std::mutex> lk(g_rec_mu);
+        if (phases == 2) {
+            auto it = g_rec.find(workspace);
+            if (it == g_rec.end())
+                return fail(ADMM_E_INVALID, "workspace holds no recording (admm_tvd_forward_grouped_record_dev_f32 first; a "
+                                            "plain forward on the same workspace overwrites it)");
+            if (!(it->second == tag))
+                return fail(ADMM_E_INVALID, "replay does not match its grouped recording (shape, grouping gb / gp / nparam, "
+                                            "PSF, iso, maxit, h_bar request or library options changed between record and "
+                                            "replay, or the recording is a single solve's)");
+            g_rec.erase(it);
+        } else if (phases == 1) {
+            g_rec[workspace] = tag;
+        } else {
+            g_rec.erase(workspace);
+        }
+    }
+    return launch_backward_grouped(phases, y, x_bar, y_bar, h_bar, lambda_bar, rho_bar, M, N, P, B, gb, gp, h, kh, kw, lambda,
+                                   rho, nparam, iso, maxit, x_out, workspace, stream, plan, gl);
 }
 
 // phases: 1 = forward recording the trajectory into the workspace (writes x_out), 2 = reverse sweep
@@ -816,6 +907,45 @@ int admm_tvd_forward_grouped_dev_f32(const float* y, float* x_out, int M, int N,
                                      int iso, int maxit, void* workspace, size_t workspace_bytes, void* stream) {
     return forward_grouped(y, x_out, M, N, P, B, gb, gp, h, kh, kw, lambda, rho, nparam, iso, maxit, workspace,
                            workspace_bytes, stream);
+}
+
+int admm_tvd_grouped_backward_workspace_bytes(int M, int N, int P, int B, int gb, int gp, int kh, int kw, int iso,
+                                              int maxit, int rec_flags, size_t* out_bytes) {
+    if (!out_bytes) return fail(ADMM_E_INVALID, "out_bytes is NULL");
+    const int rc = check_grouped(M, N, P, B, gb, gp, kh, kw, iso);
+    if (rc) return rc;
+    if (maxit < 0) return fail(ADMM_E_INVALID, "maxit must be >= 0");
+    // (nparam = G: the larger (rho_bar, tau_bar) partial block; a call with one pair fits too)
+    const GroupedPlan pl = plan_grouped_adjoint(M, N, iso != 0, kh > 0, (size_t)P * B, (rec_flags & ADMM_REC_HBAR) != 0);
+    const size_t a = make_grouped_bwd_layout(M, N, P, B, gb, gp, gb * gp, kh, kw, maxit, pl.want_h, iso != 0).total;
+    const size_t b = make_grouped_bwd_layout(M, N, P, B, gb, gp, 1, kh, kw, maxit, pl.want_h, iso != 0).total;
+    *out_bytes = a > b ? a : b;
+    return ADMM_OK;
+}
+
+int admm_tvd_forward_grouped_record_dev_f32(const float* y, float* x_out, int M, int N, int P, int B, int gb, int gp,
+                                            const float* h, int kh, int kw, const float* lambda, const float* rho,
+                                            int nparam, int iso, int maxit, int rec_flags, void* workspace,
+                                            size_t workspace_bytes, void* stream) {
+    return run_backward_grouped(1, rec_flags, y, nullptr, nullptr, nullptr, nullptr, nullptr, M, N, P, B, gb, gp, h, kh,
+                                kw, lambda, rho, nparam, iso, maxit, x_out, workspace, workspace_bytes, stream);
+}
+
+int admm_tvd_backward_grouped_recorded_dev_f32(const float* y, const float* x_bar, float* y_bar, float* h_bar,
+                                               float* lambda_bar, float* rho_bar, int M, int N, int P, int B, int gb,
+                                               int gp, const float* h, int kh, int kw, const float* lambda,
+                                               const float* rho, int nparam, int iso, int maxit, const float* x_out,
+                                               void* workspace, size_t workspace_bytes, void* stream) {
+    return run_backward_grouped(2, 0, y, x_bar, y_bar, h_bar, lambda_bar, rho_bar, M, N, P, B, gb, gp, h, kh, kw, lambda,
+                                rho, nparam, iso, maxit, const_cast<float*>(x_out), workspace, workspace_bytes, stream);
+}
+
+int admm_tvd_backward_grouped_dev_f32(const float* y, const float* x_bar, float* y_bar, float* h_bar, float* lambda_bar,
+                                      float* rho_bar, int M, int N, int P, int B, int gb, int gp, const float* h, int kh,
+                                      int kw, const float* lambda, const float* rho, int nparam, int iso, int maxit,
+                                      float* x_out, void* workspace, size_t workspace_bytes, void* stream) {
+    return run_backward_grouped(3, 0, y, x_bar, y_bar, h_bar, lambda_bar, rho_bar, M, N, P, B, gb, gp, h, kh, kw, lambda,
+                                rho, nparam, iso, maxit, x_out, workspace, workspace_bytes, stream);
 }
 
 int admm_tvd_multi_workspace_bytes(int M, int N, int P, int B, int nbranch, int maxit, int flags, size_t* out_bytes) {

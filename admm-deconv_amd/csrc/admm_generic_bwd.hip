@@ -48,8 +48,8 @@ __global__ __launch_bounds__(256) void line_adj_kernel(const float* __restrict__
                                                        const float* __restrict__ sb_in, float* __restrict__ sb_out,
                                                        float* __restrict__ vsum, float2* __restrict__ spec,
                                                        double* __restrict__ part, const float2* __restrict__ twM,
-                                                       FPlan pM, int N, int Tg, const float* __restrict__ prm) {
-    const float tau = prm[0]; const float rho = prm[1];   // device-resident scalars (setup_kernel)
+                                                       FPlan pM, int N, int Tg, const float* __restrict__ prm,
+                                                       Branches br = kOneSolve) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int M = pM.n, H = M / 2 + 1;
     const size_t MN = (size_t)M * N;
@@ -60,6 +60,8 @@ __global__ __launch_bounds__(256) void line_adj_kernel(const float* __restrict__
     float* V = reinterpret_cast<float*>(smem_raw);              // vbar lines j0-1 .. j0+T (aliases A, B)
     const XBlk xb = xcd_block();   // XCD-aware block order (admm_kernels.hip): neighbours share L2 lines
     const int plane = xb.y, j0 = xb.x * Tg;
+    if (br.nbr == 0) prm += (size_t)plane::group_of(br, plane) * br.prm_f;   // a grouped solve: the plane's group scalars
+    const float tau = prm[0]; const float rho = prm[1];   // device-resident scalars (setup_kernel)
     const int T = min(Tg, N - j0);   // the last block of a plane may be ragged (gen_nb)
     const size_t poff = (size_t)plane * 2 * MN;
     const float* vp = vb + (size_t)plane * MN;

@@ -201,12 +201,13 @@ __global__ __launch_bounds__(kThreads) void setup_grouped_kernel(float2* __restr
                                                                  int N, const float* __restrict__ lam,
                                                                  const float* __restrict__ rho, int nparam,
                                                                  float* __restrict__ prm, unsigned tab_f,
-                                                                 unsigned prm_f) {
+                                                                 unsigned prm_f, double2* __restrict__ SigT = nullptr) {
+    // SigT (a grouped recording with h_bar): group g's top-left PSF spectrum, (M/2 + 1) N double2 per group
     const size_t g = blockIdx.y;
     const size_t gs = nparam > 1 ? g : 0;
     const ScalarSrc sc{lam + gs, rho + gs, 0.f, 0.f};
     setup_body(twM, twN, Ct + g * tab_f, Gt ? Gt + g * tab_f : nullptr, h ? h + g * (size_t)kh * kw : nullptr, kh, kw, M,
-               N, sc, prm + g * prm_f, nullptr, g == 0);
+               N, sc, prm + g * prm_f, SigT ? SigT + g * (size_t)(M / 2 + 1) * N : nullptr, g == 0);
 }
 
 // ----------------------------------------------------------------------------------------------

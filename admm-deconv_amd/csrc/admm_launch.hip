@@ -180,6 +180,16 @@ int launch_column_t(int N, dim3 g, size_t lds, hipStream_t s, const float2* src,
     return -1;
 }
 
+// The grouped adjoint's GRP instantiations (modes 0, 2, 4, 7 and the line adjoint) are named at the end of this file,
+// so that they land behind every existing kernel in the code object.
+int launch_column_grouped_adj(int N, int mode, dim3 g, size_t lds, hipStream_t s, const float2* src, float2* dst,
+                              const float* C, const float2* G, const float2* twN, int L, int KB, float cs, float2* vsave,
+                              double* Qp, const Branches& br, float2* yh);
+int launch_line_adj_grouped(int L, int T, dim3 g, size_t lds, hipStream_t s, const float2* spec1, const float* sk1,
+                            const float* sk, const float* xK, const float* sb_in, float* sb_out, float* vsum, float2* spec0,
+                            double* part, const float2* twM, int N, const float* prm, int first_k, int last_k, bool ln,
+                            const Branches& br);
+
 // mode: 0 = x-update C, 1 = conj(Sigma_c) (H^T), 2 = Sigma_c (H), 3 = C + save spectrum, 4 = C + accumulate Q;
 // 5 = Y_h = cs conj(Sigma_c) F y stored to yh (G NULL: Y_h = cs F y), no inverse; 6 = + yh, x C; 7 = + yh, save, x C
 // (admm_kernels.hip YH_STORE / YH_ADD: H^T y in the spectral domain); br: several branches (C per branch, br.tab_f
@@ -187,10 +197,10 @@ int launch_column_t(int N, dim3 g, size_t lds, hipStream_t s, const float2* src,
 int launch_column(int N, int mode, dim3 g, size_t lds, hipStream_t s, const float2* src, float2* dst,
                   const float* C, const float2* G, const float2* twN, int L, int KB, float cs,
                   float2* vsave = nullptr, double* Qp = nullptr, const Branches& br = kOneSolve, float2* yh = nullptr) {
-    if (br.nbr == 0) {   // a grouped solve (forward only: Y_h prep and the x-update)
+    if (br.nbr == 0) {   // a grouped solve: Y_h prep and the x-update; the recording's and the sweep's modes below
         if (mode == 5) return launch_column_t<1, false, false, YH_STORE, true>(N, g, lds, s, src, dst, C, G, twN, L, KB, cs, vsave, Qp, br, yh);
         if (mode == 6) return launch_column_t<0, false, false, YH_ADD, true>(N, g, lds, s, src, dst, C, G, twN, L, KB, cs, vsave, Qp, br, yh);
-        return -1;
+        return launch_column_grouped_adj(N, mode, g, lds, s, src, dst, C, G, twN, L, KB, cs, vsave, Qp, br, yh);
     }
     switch (mode) {
         case 5: return launch_column_t<1, false, false, YH_STORE>(N, g, lds, s, src, dst, C, G, twN, L, KB, cs, vsave, Qp, br, yh);
@@ -425,14 +435,16 @@ TwoPass two_pass_multi(Launcher& ln, int P, int B, int nbr, size_t planes, int T
     return c;
 }
 
-// dst = F^-1 [multiplier] F src, spectrally (mode 1: conj(Sigma_c), H^T; 2: Sigma_c, H; launch_column)
-int two_pass_conv(const TwoPass& c, int cls, int mode, const float* src, float* dst) {
+// dst = F^-1 [multiplier] F src, spectrally (mode 1: conj(Sigma_c), H^T; 2: Sigma_c, H; launch_column); br: a
+// grouped solve's descriptor (mode 2: every plane with its group's G table)
+int two_pass_conv(const TwoPass& c, int cls, int mode, const float* src, float* dst, const Branches& br = kOneSolve) {
     Launcher& ln = c.ln;
     hipStream_t s = ln.s;
     int rc = ln.run(cls, [&] { return launch_line_fwd(c.L, c.T, c.gl, c.flds, s, src, c.spec0, c.twM, c.N); });
     if (rc) return rc;
     rc = ln.run(cls, [&] {
-        return launch_column(c.N, mode, c.gc, c.clds, s, c.spec0, c.spec1, c.C, c.G, c.twN, c.L, c.KB, 1.0f);
+        return launch_column(c.N, mode, c.gc, c.clds, s, c.spec0, c.spec1, c.C, c.G, c.twN, c.L, c.KB, 1.0f, nullptr,
+                             nullptr, br);
     });
     if (rc) return rc;
     return ln.run(cls, [&] { return launch_line_inv(c.L, c.T, c.gl, c.flds, s, c.spec1, dst, c.twM, c.N); });
@@ -592,7 +604,7 @@ int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t
             while (gx > 1 && gx > grid / 8 && (size_t)G * (gx / 2) >= 2048) gx /= 2;
             set_lds(admm::setup_grouped_kernel, lds);
             hipLaunchKernelGGL(admm::setup_grouped_kernel, dim3(gx, (unsigned)G), dim3(kThreads), lds, s, v.twM, v.twN,
-                               v.C, v.G, h, kh, kw, M, N, sc.lam, sc.rho, br.prm_f ? G : 1, v.prm, br.tab_f, br.prm_f);
+                               v.C, v.G, h, kh, kw, M, N, sc.lam, sc.rho, br.prm_f ? G : 1, v.prm, br.tab_f, br.prm_f, tr.sig);
             return;
         }
         set_lds(admm::setup_kernel, lds);
@@ -623,6 +635,9 @@ int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t
         Branches bf = br;
         bf.tab_f = (unsigned)(pk::grouped_tables_bytes() / 4);
         rc = ln.run(ADMM_K_PLANE, [&] {
+            if (grp && tr.s)   // a grouped recording (plane_grouped_rec.hip)
+                return pk::launch_plane_grouped_rec(y, x_out, v.F, kh > 0, v.spec0, reinterpret_cast<float4*>(v.s[0]), v.prm,
+                                                    maxit, planes, s, reinterpret_cast<float4*>(tr.s), bf);
             return pk::launch_plane(y, x_out, v.F, kh > 0, v.spec0, reinterpret_cast<float4*>(v.s[0]), v.prm, maxit,
                                    planes, s, tr.m ? nullptr : reinterpret_cast<float4*>(tr.s), grp ? &bf : nullptr, tr.m);
         });
@@ -702,7 +717,8 @@ int gen_line_inv(Launcher& ln, const GenPass& p, const FwdView& v, int cls, cons
 }
 
 // dst = F^-1 [multiplier] F src with the runtime-length kernels (mode 1: conj(Sigma_c), H^T; 2: Sigma_c, H)
-int gen_conv(Launcher& ln, const GenPass& p, const FwdView& v, int cls, int mode, const float* src, float* dst) {
+int gen_conv(Launcher& ln, const GenPass& p, const FwdView& v, int cls, int mode, const float* src, float* dst,
+             const Branches& br = kOneSolve) {
     int rc = gen_line_fwd(ln, p, v, cls, src, v.spec0);
     if (rc) return rc;
     rc = ln.run(cls, [&] {
@@ -710,7 +726,7 @@ int gen_conv(Launcher& ln, const GenPass& p, const FwdView& v, int cls, int mode
             return admm::sm::launch_column(p.M, p.N, p.planes, ln.s, v.spec0, v.spec1, v.C, v.G, v.twN, 1.0f, mode,
                                            opt(ADMM_OPT_SMOOTH));
         hipLaunchKernelGGL(admm::gen::column_kernel, p.gc, dim3(256), p.lcol, ln.s, v.spec0, v.spec1, v.C, v.G, v.twN, p.pN,
-                           p.H, p.KB, mode, 1.0f);
+                           p.H, p.KB, mode, 1.0f, (float2*)nullptr, (double*)nullptr, (float2*)nullptr, br);
         return 0;
     });
     if (rc) return rc;
@@ -819,6 +835,9 @@ int launch_line_adj(int L, int T, dim3 g, size_t lds, hipStream_t s, const float
                     const float* sk, const float* xK, const float* sb_in, float* sb_out, float* vsum, float2* spec0,
                     double* part, const float2* twM, int N, const float* prm, int first_k, int last_k, bool ln,
                     const Branches& br = kOneSolve, size_t pbs = 0) {
+    if (br.nbr == 0)   // a grouped solve: the plane's group scalars, rows by plane
+        return launch_line_adj_grouped(L, T, g, lds, s, spec1, sk1, sk, xK, sb_in, sb_out, vsum, spec0, part, twM, N, prm,
+                                       first_k, last_k, ln, br);
     if (ln) {   // trajectory in the fused kernel's lane-native layout (M = 256)
 #define X(l, t)                                                                                                \
         if (L == l && T == t) {                                                                                \
@@ -899,6 +918,8 @@ RevStep rev_step(int k, int K, const SweepBufs& b, size_t sstride, size_t nstrid
 // spectrum of the step and the Q accumulators) and the line adjoint -- or, isotropic, ISO_ADJ_A (plane groups) ->
 // ISO_ADJ_R (batch R map, tau_bar) -> ISO_ADJ_B (per plane); k = 1 launches no ISO_ADJ_R or _B.
 // ln_traj: the trajectory is in the fused kernel's lane-native layout (M = 256, anisotropic)
+// A grouped solve (c.br.nbr = 0): the column pass takes the plane's group C table and the line adjoint its group
+// scalars; the isotropic adjoint kernels keep c.bro -- an isotropic grouped solve has one (lambda, rho) pair, in block 0.
 int two_pass_reverse(const TwoPass& c, const SweepBufs& b, const float* x_bar, int K, bool iso, bool ln_traj,
                      const admm_batch_reducer* red = nullptr) {
     Launcher& ln = c.ln;
@@ -913,7 +934,7 @@ int two_pass_reverse(const TwoPass& c, const SweepBufs& b, const float* x_bar, i
         float2* vs = b.v ? b.v + (size_t)(k - 1) * c.planes * c.N * c.L : nullptr;
         rc = ln.run(ADMM_K_COLUMN, [&] {
             return launch_column(c.N, b.v ? 4 : 0, c.gc, c.clds, s, c.spec0, c.spec1, c.C, c.G, c.twN, c.L, c.KB, 1.0f, vs,
-                                 b.Qp, c.bro);
+                                 b.Qp, c.br);
         });
         if (rc) return rc;
         const RevStep r = rev_step(k, K, b, sstride, c.nstride, c.rows);
@@ -921,7 +942,7 @@ int two_pass_reverse(const TwoPass& c, const SweepBufs& b, const float* x_bar, i
         if (!iso) {
             rc = ln.run(ADMM_K_ADJ, [&] {
                 return launch_line_adj(c.L, c.T, c.gl, alds, s, c.spec1, r.sk1, skk, b.xK, r.sbi, r.sbo, b.vsum, c.spec0,
-                                       r.rp, c.twM, c.N, c.prm, k == 1 ? 1 : 0, k == K ? 1 : 0, ln_traj, c.bro, c.pbs);
+                                       r.rp, c.twM, c.N, c.prm, k == 1 ? 1 : 0, k == K ? 1 : 0, ln_traj, c.br, c.pbs);
             });
             if (rc) return rc;
             continue;
@@ -955,9 +976,11 @@ int two_pass_reverse(const TwoPass& c, const SweepBufs& b, const float* x_bar, i
 
 // The runtime-length reverse sweep (admm_generic_bwd.hip): per step column, line inverse -> vbar_k in HBM (the
 // forward's x slot), then the line adjoint (aniso) or ISO_ADJ_A -> ISO_ADJ_R -> ISO_ADJ_B.  These kernels take s_k and
-// x_K (rho_bar's terms) whether or not rho_bar is wanted.
+// x_K (rho_bar's terms) whether or not rho_bar is wanted.  br: a grouped solve's descriptor (the column pass and the
+// line adjoint look the plane's group up; the isotropic kernels read the one scalar block).
 int runtime_reverse(Launcher& ln, const GenPass& p, const FwdView& v, const SweepBufs& b, const float* x_bar,
-                    const float* xK, int K, bool iso, int rows, int r_off, const admm_batch_reducer* red) {
+                    const float* xK, int K, bool iso, int rows, int r_off, const admm_batch_reducer* red,
+                    const Branches& br = kOneSolve) {
     namespace g = admm::gen;
     hipStream_t s = ln.s;
     const int M = p.M, N = p.N;
@@ -972,7 +995,7 @@ int runtime_reverse(Launcher& ln, const GenPass& p, const FwdView& v, const Swee
         float2* vs = b.v ? b.v + (size_t)(k - 1) * p.planes * N * p.H : nullptr;
         rc = ln.run(ADMM_K_COLUMN, [&] {
             hipLaunchKernelGGL(g::column_kernel, p.gc, dim3(256), p.lcol, s, v.spec0, v.spec1, v.C, v.G, v.twN, p.pN, p.H,
-                               p.KB, b.v ? 8 : 0, 1.0f, vs, b.Qp);
+                               p.KB, b.v ? 8 : 0, 1.0f, vs, b.Qp, (float2*)nullptr, br);
         });
         if (rc) return rc;
         rc = gen_line_inv(ln, p, v, ADMM_K_LINE, v.spec1, vb);
@@ -981,7 +1004,7 @@ int runtime_reverse(Launcher& ln, const GenPass& p, const FwdView& v, const Swee
         if (!iso) {
             rc = ln.run(ADMM_K_ADJ, [&] {
                 hipLaunchKernelGGL(g::line_adj_kernel, p.gl, dim3(256), p.lup, s, vb, r.sk1, r.skk, xK, r.sbi, r.sbo,
-                                   b.vsum, v.spec0, r.rp, v.twM, p.pM, N, p.T, v.prm);
+                                   b.vsum, v.spec0, r.rp, v.twM, p.pM, N, p.T, v.prm, br);
             });
             if (rc) return rc;
             continue;
@@ -1348,6 +1371,161 @@ int launch_backward_multi(const float* x_bar, float* y_bar, float* lambda_bar, f
     if (rc) return rc;
     return ln.finish();
 }
+
+// ---- grouped adjoint (admm_tvd_backward_grouped_*) ---------------------------------------------------------------
+// One recorded forward and one reverse sweep over every plane, each with its group's tables and scalars (plan:
+// admm_paths.hip plan_grouped_adjoint), then the per-group assembly (admm_backward.hip, last section).  The workspace
+// is a BwdLayout whose table, scalar, sig, Q, hcorr, hA and rt slots are the per-group blocks (GroupedBwdLayout).
+
+// group-segmented column sums of partial rows [step][plane][blk] x w -> out[group][w] (reduce_groups_kernel)
+void launch_reduce_groups(hipStream_t s, const double* part, double* out, int nsteps, size_t step_rows, int nblk, int w,
+                          const Branches& br, int groups, int split, double* tmp) {
+    const long long n = ((long long)nsteps * admm::group_planes(br) * nblk + split - 1) / split;
+    const int nt = n <= 64 ? 64 : kThreads;
+    hipLaunchKernelGGL(admm::reduce_groups_kernel, dim3(w, groups, split), dim3(nt), 0, s, part, split > 1 ? tmp : out,
+                       nsteps, step_rows, nblk, w, br);
+    if (split > 1)
+        hipLaunchKernelGGL(admm::reduce_groups_fin_kernel, dim3((groups * w + 255) / 256), dim3(256), 0, s, tmp, out, split,
+                           w, groups * w);
+}
+
+int launch_backward_grouped(int phases, const float* y, const float* x_bar, float* y_bar, float* h_bar,
+                            float* lambda_bar, float* rho_bar, int M, int N, int P, int B, int gb, int gp, const float* h,
+                            int kh, int kw, const float* lambda, const float* rho, int nparam, int iso, int maxit,
+                            float* x_out, void* workspace, void* stream, const GroupedPlan& plan,
+                            const GroupedBwdLayout& gl) {
+    int rc = ADMM_OK;
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    Launcher ln{s, g_prof.on, {}};
+    const size_t planes = (size_t)P * B, MN = (size_t)M * N;
+    const int K = maxit, G = gb * gp, ntaps = kh * kw;
+    const BwdLayout& bl = gl.b;
+    if (K == 0) {
+        if (phases & 2) {
+            if (y_bar) HIPCHK(hipMemsetAsync(y_bar, 0, planes * MN * 4, s));
+            if (h_bar && kh > 0) HIPCHK(hipMemsetAsync(h_bar, 0, (size_t)G * ntaps * 4, s));
+            if (lambda_bar) HIPCHK(hipMemsetAsync(lambda_bar, 0, (size_t)nparam * 4, s));
+            if (rho_bar) HIPCHK(hipMemsetAsync(rho_bar, 0, (size_t)nparam * 4, s));
+        }
+        if (phases & 1) HIPCHK(hipMemsetAsync(x_out, 0, planes * MN * 4, s));
+        return ln.finish();
+    }
+    const Branches br = admm::plane::grouped_branches(P, B, gb, gp, gl.tab_f, nparam > 1 ? 4u : 0u);
+    const bool want_v = y_bar != nullptr || (h_bar != nullptr && kh > 0);
+    const BwdView v = view(ws, bl, kh > 0, iso != 0, plan.want_h, want_v, rho_bar ? x_out : nullptr);
+    const SweepBufs& b = v.b;
+    // ---- forward with trajectory (s_k natural or, from the fused kernel, lane-native; with h_bar the dim-2 spectra
+    // and every group's PSF spectrum) ----
+    Traj tr;
+    tr.s = const_cast<float*>(b.traj);
+    tr.v = b.v;
+    tr.sig = v.sig;
+    tr.nrm = const_cast<float*>(b.nrm);
+    if (phases & 1) {
+        rc = run_forward(ln, y, x_out, M, N, planes, h, kh, kw, admm::ScalarSrc{lambda, rho, 0.f, 0.f}, iso, K, ws, bl.f, tr,
+                         nullptr, plan.fwd, true, &br);
+        if (rc) return rc;
+    }
+    if (!(phases & 2)) return ln.finish();
+    // ---- reverse sweep: the replay uses the tables and scalar blocks the recording left in the workspace ----
+    if (b.vsum) HIPCHK(hipMemsetAsync(b.vsum, 0, planes * MN * 4, s));
+    if (iso) HIPCHK(hipMemsetAsync(b.part, 0, (size_t)K * bl.nblk_line * 2 * 8, s));   // k = 1: no ISO_ADJ_R rows
+    if (b.Qp) HIPCHK(hipMemsetAsync(b.Qp, 0, planes * (size_t)(M / 2 + 1) * N * 8, s));
+    const bool gen = generic_shape(M, N);
+    const GenPass gpass = gen ? gen_pass(M, N, planes, false) : GenPass{};
+    auto grid = [&] {
+        TwoPass c = two_pass_single(ln, M, N, planes, bwd_line_T(M, N, iso != 0), v.f, br);
+        c.rows = bl.nblk_line, c.r_off = bl.nblk_isoA;
+        return c;
+    };
+    if (gen) rc = runtime_reverse(ln, gpass, v.f, b, x_bar, x_out, K, iso != 0, bl.nblk_line, bl.nblk_isoA, nullptr, br);
+    else rc = two_pass_reverse(grid(), b, x_bar, K, iso != 0, plan.ln_traj);
+    if (rc) return rc;
+    // ---- assembly ----
+    // (rho_bar, tau_bar): isotropic -- one pair, every row; anisotropic -- per (lambda, rho) group, its planes' rows
+    const Branches all{P * B, 0, P, 0u, 0u, 0, 0};   // one pair for every group: one segment of all planes
+    rc = ln.run(ADMM_K_FINAL, [&] {
+        if (iso) launch_reduce_cols(s, b.part, v.rt, K * bl.nblk_line, 2, v.rtmp);
+        else launch_reduce_groups(s, b.part, v.rt, K, (size_t)bl.nblk_line, bl.nblk_line / (int)planes, 2,
+                                  nparam > 1 ? br : all, nparam, gl.split_rt, at<double>(ws, gl.gtmp));
+    });
+    if (rc) return rc;
+    if (kh > 0 && b.vsum) {
+        if (y_bar) {   // y_bar = H_g Vsum: every plane with its group's G table
+            rc = gen ? gen_conv(ln, gpass, v.f, ADMM_K_FINAL, 2, b.vsum, y_bar, br)
+                     : two_pass_conv(grid(), ADMM_K_FINAL, 2, b.vsum, y_bar, br);
+            if (rc) return rc;
+        }
+        if (h_bar) {
+            rc = ln.run(ADMM_K_FINAL, [&] {
+                const size_t lds = (size_t)(2 * bl.TY + kw - 1) * M * 4;
+                set_lds(admm::hbar_corr_kernel, lds);
+                hipLaunchKernelGGL(admm::hbar_corr_kernel, dim3(N / bl.TY, (unsigned)planes), dim3(kThreads), lds, s,
+                                   b.vsum, y, v.hpart, M, N, kh, kw, bl.TY);
+            });
+            if (rc) return rc;
+            rc = ln.run(ADMM_K_FINAL, [&] {
+                launch_reduce_groups(s, v.hpart, v.hcorr, 1, 0, N / bl.TY, ntaps, br, G, gl.split_h, at<double>(ws, gl.gtmp));
+            });
+            if (rc) return rc;
+            const int nq = (M / 2 + 1) * N;
+            rc = ln.run(ADMM_K_FINAL, [&] {
+                hipLaunchKernelGGL(admm::reduce_planes_grouped_kernel, dim3((nq + 255) / 256, (unsigned)G), dim3(256), 0, s,
+                                   b.Qp, v.Q, nq, br);
+            });
+            if (rc) return rc;
+            rc = ln.run(ADMM_K_FINAL, [&] {
+                hipLaunchKernelGGL(admm::hbarA_grouped_kernel, dim3(ntaps, (unsigned)G), dim3(kThreads), 0, s, v.Q, v.f.C,
+                                   v.sig, kh, ntaps, M, N, v.hA, gl.tab_f);
+            });
+            if (rc) return rc;
+        }
+    } else if (y_bar) {
+        HIPCHK(hipMemcpyAsync(y_bar, b.vsum, planes * MN * 4, hipMemcpyDeviceToDevice, s));
+    }
+    rc = ln.run(ADMM_K_FINAL, [&] {
+        const int nt = ntaps > 1 ? ntaps : 1;
+        const bool hb = h_bar && kh > 0;
+        hipLaunchKernelGGL(admm::grads_final_grouped_kernel, dim3((nt + 255) / 256, (unsigned)G), dim3(256), 0, s, v.rt,
+                           hb ? v.hcorr : nullptr, hb ? v.hA : nullptr, ntaps, v.f.prm, br.prm_f, nparam, lambda_bar,
+                           rho_bar, hb ? h_bar : nullptr);
+    });
+    if (rc) return rc;
+    return ln.finish();
+}
 #undef HIPCHK
+
+// ---- the grouped adjoint's instantiations of the 2-pass kernels (last: see "template dispatch" above) ----
+int launch_column_grouped_adj(int N, int mode, dim3 g, size_t lds, hipStream_t s, const float2* src, float2* dst,
+                              const float* C, const float2* G, const float2* twN, int L, int KB, float cs, float2* vsave,
+                              double* Qp, const Branches& br, float2* yh) {
+    switch (mode) {
+        case 0: return launch_column_t<0, false, false, YH_NONE, true>(N, g, lds, s, src, dst, C, G, twN, L, KB, cs, vsave, Qp, br);
+        case 2: return launch_column_t<2, false, false, YH_NONE, true>(N, g, lds, s, src, dst, C, G, twN, L, KB, cs, vsave, Qp, br);
+        case 4: return launch_column_t<0, false, true, YH_NONE, true>(N, g, lds, s, src, dst, C, G, twN, L, KB, cs, vsave, Qp, br);
+        case 7: return launch_column_t<0, true, false, YH_ADD, true>(N, g, lds, s, src, dst, C, G, twN, L, KB, cs, vsave, Qp, br, yh);
+    }
+    return -1;
+}
+
+int launch_line_adj_grouped(int L, int T, dim3 g, size_t lds, hipStream_t s, const float2* spec1, const float* sk1,
+                            const float* sk, const float* xK, const float* sb_in, float* sb_out, float* vsum, float2* spec0,
+                            double* part, const float2* twM, int N, const float* prm, int first_k, int last_k, bool ln,
+                            const Branches& br) {
+#define XG(l, t, lane)                                                                                               \
+    if (L == l && T == t && ln == lane) {                                                                            \
+        set_lds(line_adj_kernel<l, t, lane, true>, lds);                                                             \
+        line_adj_kernel<l, t, lane, true><<<g, kThreads, lds, s>>>(spec1, sk1, sk, xK, sb_in, sb_out, vsum, spec0,   \
+                                                                    part, twM, N, prm, first_k, last_k, br, 0);      \
+        return 0;                                                                                                    \
+    }
+#define X(l, t) XG(l, t, false)
+    ADMM_LT_CASES(X)
+#undef X
+    XG(128, 2, true) XG(128, 4, true) XG(128, 8, true) XG(128, 16, true)
+#undef XG
+    return -1;
+}
 
 }  // namespace admm_capi

@@ -214,6 +214,24 @@ int plan_grouped(int M, int N, bool iso, size_t planes) {
     return iso ? ADMM_PATH_2PASS_ISO : ADMM_PATH_2PASS;
 }
 
+// Grouped adjoint: the recording forward and the reverse sweep of a grouped call (capi_internal.hpp GroupedPlan).  The
+// fused forward records s only (no dim-2 spectra), so a recording for h_bar takes the 2-pass forward; the sweep is
+// always the 2-pass / runtime-length one, whose kernels take the plane -> group map.
+GroupedPlan plan_grouped_adjoint(int M, int N, bool iso, bool psf, size_t planes, bool want_h) {
+    GroupedPlan pl;
+    pl.want_h = want_h && psf;
+    if (generic_shape(M, N)) {
+        pl.fwd = ADMM_PATH_RUNTIME;
+        pl.bwd = iso ? ADMM_PATH_SWEEP_RUNTIME_ISO : ADMM_PATH_SWEEP_RUNTIME;
+        return pl;
+    }
+    const PathIn q{M, N, iso, psf, ADMM_MODE_RECORD, 0, false, false, planes};
+    pl.ln_traj = fused_shape(M, N, iso) && fused_enabled() && !pl.want_h && enough_planes(q, kMinFused);
+    pl.fwd = pl.ln_traj ? ADMM_PATH_FUSED : iso ? ADMM_PATH_2PASS_ISO : ADMM_PATH_2PASS;
+    pl.bwd = iso ? ADMM_PATH_SWEEP_2PASS_ISO : ADMM_PATH_SWEEP_2PASS;
+    return pl;
+}
+
 // lines per block: the largest of 8, 4, 2, 1 dividing N with T * M <= 4096 (LDS ~ 24 T M bytes)
 // options ADMM_OPT_GEN_TM (max T x M of a line block), ADMM_OPT_GEN_KN (max KB x N of a column block)
 int gen_opt(int k, int dflt) {
@@ -298,6 +316,28 @@ int admm_query_grouped_path(int M, int N, int iso, int kh, long long planes, int
     if (planes < 0 || groups < 1 || (planes > 0 && groups > planes))
         return fail(ADMM_E_INVALID, "admm_query_grouped_path: planes must be >= 0 and 1 <= groups <= planes");
     *fwd_path = plan_grouped(M, N, iso != 0, (size_t)planes);
+    return ADMM_OK;
+}
+
+int admm_query_grouped_paths(int M, int N, int iso, int kh, long long planes, int groups, int mode, int flags,
+                             int want_hbar, int want_rho, int* fwd_path, int* bwd_path) {
+    (void)want_rho;   // (the grouped sweeps form rho_bar from the same trajectory: it does not change the paths)
+    if (!fwd_path || !bwd_path) return fail(ADMM_E_INVALID, "admm_query_grouped_paths: NULL output");
+    if (mode != ADMM_MODE_FORWARD && mode != ADMM_MODE_RECORD && mode != ADMM_MODE_BACKWARD)
+        return fail(ADMM_E_INVALID, "admm_query_grouped_paths: unknown mode %d", mode);
+    const int rc = check_shape(M, N, 1, 1, kh, kh > 0 ? 1 : 0, iso);   // (kw is not given: any kw <= N)
+    if (rc) return rc;
+    if (planes < 0 || groups < 1 || (planes > 0 && groups > planes))
+        return fail(ADMM_E_INVALID, "admm_query_grouped_paths: planes must be >= 0 and 1 <= groups <= planes");
+    if (mode == ADMM_MODE_FORWARD) {
+        *fwd_path = plan_grouped(M, N, iso != 0, (size_t)planes);
+        *bwd_path = 0;
+        return ADMM_OK;
+    }
+    const bool want_h = mode == ADMM_MODE_RECORD ? (flags & ADMM_REC_HBAR) != 0 : want_hbar != 0;
+    const GroupedPlan pl = plan_grouped_adjoint(M, N, iso != 0, kh > 0, (size_t)planes, want_h);
+    *fwd_path = pl.fwd;
+    *bwd_path = pl.bwd;
     return ADMM_OK;
 }
 

@@ -235,6 +235,40 @@ struct GroupedLayout {
 };
 GroupedLayout make_grouped_layout(int M, int N, size_t planes, int groups, bool psf, bool iso);
 
+// ---- grouped adjoint (admm_tvd_backward_grouped_*) ----
+// One path decision (admm_paths.hip), reported by admm_query_grouped_paths: runtime-length shapes record with the
+// runtime-length forward and sweep with sweep_runtime(_iso); 256 x 256 anisotropic from the plane-count rule, fused
+// enabled and no h_bar trajectory records lane-native s with the fused forward and sweeps with sweep_2pass (ln_traj);
+// everything else is the 2-pass forward and sweep_2pass(_iso).  Never the fused reverse sweeps (one table set), the
+// smooth-length or resident kernels, or the MALL chunk schedule.
+struct GroupedPlan {
+    int fwd = 0, bwd = 0;    // ADMM_PATH_* / ADMM_PATH_SWEEP_*
+    bool want_h = false;     // the dim-2 spectra and the groups' PSF spectra are recorded (h_bar)
+    bool ln_traj = false;    // the fused forward records s lane-native
+};
+GroupedPlan plan_grouped_adjoint(int M, int N, bool iso, bool psf, size_t planes, bool want_h);
+// Workspace: a BwdLayout of the whole batch, behind it the grouped table blocks of GroupedLayout and, per group, sig
+// (PSF spectrum), Q, hcorr, hA and rt; b.f.prm / C / G / F and b.sig / Q / hcorr / hA / rt name those blocks (the
+// layout's own single-set slots stay allocated and unused).  gtmp: the split partials of the group-segmented sums.
+struct GroupedBwdLayout {
+    BwdLayout b;
+    unsigned tab_f;
+    size_t gtmp, total;
+    int split_rt, split_h;   // parts a group's (rho_bar, tau_bar) rows / h_bar correlation rows are summed in
+};
+GroupedBwdLayout make_grouped_bwd_layout(int M, int N, int P, int B, int gb, int gp, int nparam, int kh, int kw, int maxit,
+                                         bool want_h, bool iso);
+// parts for a fixed-order sum of n rows: about 4096 rows per block, at most 256 parts
+inline int group_split(long long n) {
+    const long long p = (n + 4095) / 4096;
+    return p < 1 ? 1 : p > 256 ? 256 : (int)p;
+}
+int launch_backward_grouped(int phases, const float* y, const float* x_bar, float* y_bar, float* h_bar,
+                            float* lambda_bar, float* rho_bar, int M, int N, int P, int B, int gb, int gp, const float* h,
+                            int kh, int kw, const float* lambda, const float* rho, int nparam, int iso, int maxit,
+                            float* x_out, void* workspace, void* stream, const GroupedPlan& plan,
+                            const GroupedBwdLayout& gl);
+
 // ---- launch sequencing (admm_launch.hip) ----
 // The four entry points below set a call up and pick its path; the 2-pass kernels' step sequences exist once
 // (two_pass_forward / two_pass_reverse on a TwoPass grid: a single or grouped solve, or the one-grid call's

@@ -92,6 +92,13 @@ hipError_t launch_plane(const float* y, float* x_out, const void* tables, bool p
                         const Branches* br = nullptr, unsigned* masks = nullptr);
 
 
+// A grouped solve (br.nbr = 0) that records s_1..s_{K-1} lane-native in `traj`, as launch_plane does for a single solve
+// (the grouped adjoint's fused trajectory; no mask-bit form).  Its kernel instantiations live in plane_grouped_rec.hip,
+// a translation unit of their own, so that the code object of the kernels above is the same with or without them.
+hipError_t launch_plane_grouped_rec(const float* y, float* x_out, const void* tables, bool psf, float2* hln, float4* sln,
+                                    const float* prm, int K, size_t planes, hipStream_t s, float4* traj,
+                                    const Branches& br);
+
 // Reverse sweep of the anisotropic solve on the fused trajectory (plane256_adj_kernel):
 // launch_dx_lane writes D x_K (x_K = the forward output, natural layout) in the lane-native s layout;
 // launch_plane_adj runs steps K..1 for every plane.  traj: the forward's s_1..s_{K-1}; sbar, vsl: planes x

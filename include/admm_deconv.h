@@ -265,6 +265,53 @@ int admm_tvd_forward_grouped_dev_f32(const float* y, float* x_out, int M, int N,
                                      void* stream);
 int admm_query_grouped_path(int M, int N, int iso, int kh, long long planes, int groups, int* fwd_path);
 
+/* Grouped adjoint: the gradients of the grouped solve per PSF / (lambda, rho) group from ONE recorded forward and ONE
+ * reverse sweep (training per-image blur kernels, per-channel PSFs, per-image noise levels).  Grouping, layouts and
+ * argument validation are exactly those of admm_tvd_forward_grouped_dev_f32; at most 65,280 planes per call; there is
+ * no sharded (reducer) form.
+ * Outputs are device pointers, NULL = not wanted (and cheaper, as in the single adjoint): y_bar `float[B][P][N][M]`;
+ * h_bar `float[G][kw][kh]`, one gradient per group's PSF; lambda_bar, rho_bar: nparam floats each -- nparam = G:
+ * entry g sums over group g's planes, nparam = 1: the entry sums over all planes.  iso = 1 keeps the forward's batch
+ * coupling (R maps and the norm over all planes, whatever their group); nparam is then 1 (nparam = G > 1:
+ * ADMM_E_UNSUPPORTED) and h_bar is still per group.
+ * The record / replay pair follows the single one's contract: rec_flags takes ADMM_REC_HBAR (record the extra
+ * trajectory h_bar needs; the replay must then be given h_bar, and only then); ADMM_REC_MASKS is accepted and not
+ * honoured (the full trajectory is recorded and rho_bar stays available).  The replay differentiates the recorded
+ * trajectory with the per-group scalar blocks left in the workspace.  ADMM_E_INVALID before any launch: a replay whose
+ * shape, grouping (gb, gp, nparam), PSF size, prox, maxit, h_bar request or library options differ from the
+ * recording's; a single-solve replay of a grouped recording and the reverse; a workspace that holds no recording (a
+ * plain grouped forward on it forgets one; a replay consumes it).  maxit = 0 zeroes every output asked for.
+ * Deterministic (no atomics: each group's partial sums are added in a fixed order), allocates nothing, asynchronous on
+ * `stream`, never modifies y.  Workspace (admm_tvd_grouped_backward_workspace_bytes): the single adjoint's layout of
+ * the whole batch plus, per group, one table set, one scalar block, the PSF spectrum, Q, the two h_bar terms and the
+ * (rho_bar, tau_bar) sums.
+ * Paths (admm_query_grouped_paths; mode / flags / want_hbar as admm_query_paths, ADMM_MODE_FORWARD reports
+ * admm_query_grouped_path and no sweep): runtime-length shapes record with ADMM_PATH_RUNTIME and sweep with
+ * ADMM_PATH_SWEEP_RUNTIME / _RUNTIME_ISO; 256 x 256 anisotropic with the fused kernels enabled, at or above their
+ * plane count and without ADMM_REC_HBAR records lane-native s with ADMM_PATH_FUSED and sweeps with
+ * ADMM_PATH_SWEEP_2PASS; everything else (256 x 256 with h_bar, below the plane count or isotropic, the other
+ * power-of-two shapes) is ADMM_PATH_2PASS / _2PASS_ISO and ADMM_PATH_SWEEP_2PASS / _2PASS_ISO.  NOT taken by grouped
+ * calls: the fused reverse sweeps (one table set), mask-bit recordings, the smooth-length and CU-resident kernels and
+ * the MALL chunk schedule. */
+int admm_tvd_grouped_backward_workspace_bytes(int M, int N, int P, int B, int gb, int gp, int kh, int kw, int iso,
+                                              int maxit, int rec_flags, size_t* out_bytes);
+int admm_tvd_forward_grouped_record_dev_f32(const float* y, float* x_out, int M, int N, int P, int B, int gb, int gp,
+                                            const float* h, int kh, int kw, const float* lambda, const float* rho,
+                                            int nparam, int iso, int maxit, int rec_flags, void* workspace,
+                                            size_t workspace_bytes, void* stream);
+int admm_tvd_backward_grouped_recorded_dev_f32(const float* y, const float* x_bar, float* y_bar, float* h_bar,
+                                               float* lambda_bar, float* rho_bar, int M, int N, int P, int B, int gb,
+                                               int gp, const float* h, int kh, int kw, const float* lambda,
+                                               const float* rho, int nparam, int iso, int maxit, const float* x_out,
+                                               void* workspace, size_t workspace_bytes, void* stream);
+/* the two back to back (x_out is written) */
+int admm_tvd_backward_grouped_dev_f32(const float* y, const float* x_bar, float* y_bar, float* h_bar, float* lambda_bar,
+                                      float* rho_bar, int M, int N, int P, int B, int gb, int gp, const float* h, int kh,
+                                      int kw, const float* lambda, const float* rho, int nparam, int iso, int maxit,
+                                      float* x_out, void* workspace, size_t workspace_bytes, void* stream);
+int admm_query_grouped_paths(int M, int N, int iso, int kh, long long planes, int groups, int mode, int flags,
+                             int want_hbar, int want_rho, int* fwd_path, int* bwd_path);
+
 /* Library options: process-global switches read at each call.  The defaults are the tuned choices;
  * the others exist for tests (fused vs 2-pass paths) and tuning experiments.  Not read from the
  * environment.  A recording remembers the options it was made with (see above). */

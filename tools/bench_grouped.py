@@ -5,6 +5,11 @@ Modes (one JSON line each; hipEvent timing, warm-up, median over the steps):
   grouped  one tvd_fft_grouped call
   loop     what users did before: 512 single-image tvd_fft calls, each with its own PSF
   ceiling  one single-PSF tvd_fft call over the same batch (every plane shares one table set)
+Training-step modes (a recorded forward and its reverse sweep with y_bar, h_bar, lambda_bar and rho_bar; x_bar = x - y):
+  train          one tvd_fft_grouped_record + tvd_fft_grouped_backward_recorded
+  train_loop     what users did before: 512 single-image tvd_fft_record + tvd_fft_backward_recorded calls
+  train_ceiling  one single-PSF tvd_fft_record + tvd_fft_backward_recorded over the same batch
+--profile: after timing a mode, one more call under the library profiler; its per-class milliseconds go into the line.
 --pkg DIR: import admm_deconv from another build of the package (e.g. the parent commit's, which has no grouped
 entry: modes loop and ceiling).  usage: bench_grouped.py [--modes grouped,loop,ceiling] [--steps 20] [--warmup 3]"""
 import argparse
@@ -25,6 +30,7 @@ ap.add_argument("--batch", type=int, default=512)
 ap.add_argument("--maxit", type=int, default=25)
 ap.add_argument("--pkg", default=os.path.join(REPO, "admm-deconv_amd"))
 ap.add_argument("--tag", default="branch")
+ap.add_argument("--profile", action="store_true")
 args = ap.parse_args()
 sys.path.insert(0, os.path.abspath(args.pkg))
 import admm_deconv  # noqa: E402
@@ -60,8 +66,38 @@ def ceiling():
     admm_deconv.tvd_fft(y, lam, rho, h[B // 2, 0], False, K, out=out)
 
 
+def train():
+    x, rec = admm_deconv.tvd_fft_grouped_record(y, lam, rho, h, False, K)
+    return admm_deconv.tvd_fft_grouped_backward_recorded(rec, x, x - y)[1]
+
+
+def train_loop():
+    for b in range(B):
+        x, rec = admm_deconv.tvd_fft_record(y[b:b + 1], lam, rho, h[b, 0], False, K)
+        admm_deconv.tvd_fft_backward_recorded(rec, x, x - y[b:b + 1])
+
+
+def train_ceiling():
+    x, rec = admm_deconv.tvd_fft_record(y, lam, rho, h[B // 2, 0], False, K)
+    return admm_deconv.tvd_fft_backward_recorded(rec, x, x - y)[1]
+
+
+def profiled(fn):
+    """Per-class milliseconds of one call under the library profiler (it synchronises: not the timed runs)."""
+    from admm_deconv import _lib
+    _lib.profile_reset()
+    _lib.profile_enable(True)
+    try:
+        fn()
+        torch.cuda.synchronize()
+        return {name: round(_lib.profile_get(c)[0], 3) for c, name in _lib.KERNEL_CLASSES.items() if _lib.profile_get(c)[1]}
+    finally:
+        _lib.profile_enable(False)
+
+
 for mode in args.modes.split(","):
-    fn = {"grouped": grouped, "loop": loop, "ceiling": ceiling}[mode]
+    fn = {"grouped": grouped, "loop": loop, "ceiling": ceiling, "train": train, "train_loop": train_loop,
+          "train_ceiling": train_ceiling}[mode]
     for _ in range(args.warmup):
         fn()
     torch.cuda.synchronize()
@@ -74,7 +110,14 @@ for mode in args.modes.split(","):
         torch.cuda.synchronize()
         ms.append(a.elapsed_time(b_))
     med = statistics.median(ms)
-    print(json.dumps({"tool": "bench_grouped", "tag": args.tag, "mode": mode, "batch": B, "maxit": K, "groups": B,
-                      "steps": args.steps, "warmup": args.warmup, "ms_median": round(med, 4), "ms_min": round(min(ms), 4),
-                      "ms_max": round(max(ms), 4), "img_per_s": round(B / med * 1e3, 1),
-                      "checksum": float(out.double().sum().item())}), flush=True)
+    line = {"tool": "bench_grouped", "tag": args.tag, "mode": mode, "batch": B, "maxit": K, "groups": B,
+            "steps": args.steps, "warmup": args.warmup, "ms_median": round(med, 4), "ms_min": round(min(ms), 4),
+            "ms_max": round(max(ms), 4), "img_per_s": round(B / med * 1e3, 1)}
+    if mode.startswith("train"):
+        hb = fn()   # (train_loop returns nothing: its gradients are per call)
+        line["checksum"] = float(hb.double().sum().item()) if hb is not None else None
+    else:
+        line["checksum"] = float(out.double().sum().item())
+    if args.profile:
+        line["profile_ms"] = profiled(fn)
+    print(json.dumps(line), flush=True)
