@@ -40,11 +40,19 @@ class Workspace:
         # + 256: room for the 256-B alignment of the returned pointer
         if self._buf is None or self._buf.numel() < nbytes + 256 or self._buf.device != device:
             self._buf = torch.empty(max(nbytes, 256) + 256, dtype=torch.uint8, device=device)
-        if stream is not None and isinstance(stream, torch.cuda.Stream) and stream != torch.cuda.current_stream(device):
-            self._buf.record_stream(stream)
+        _record_streams(stream, device, self._buf)
         ptr = self._buf.data_ptr()
         off = (-ptr) % 256
         return ptr + off, self._buf.numel() - off
+
+
+def _record_streams(stream, device, *tensors):
+    """Mark tensors as used on `stream` when it is a torch stream other than the current one (the caching allocator
+    must not hand their memory on before that stream is done).  The only place that compares streams."""
+    if isinstance(stream, torch.cuda.Stream) and stream != torch.cuda.current_stream(device):
+        for t in tensors:
+            if t is not None:
+                t.record_stream(stream)
 
 
 # default workspaces, one per (kind, device, stream): concurrent solves on different streams (e.g. the
@@ -58,6 +66,14 @@ def _default_workspace(kind, device, stream):
 
 def _stream_handle(stream):
     return stream.cuda_stream if hasattr(stream, "cuda_stream") else int(stream)
+
+
+def _acquire(kind, nbytes, device, stream, workspace=None):
+    """(workspace, pointer, length) of nbytes of scratch on `stream`: the caller's workspace (a recording's own), or
+    the default one of this kind of call."""
+    if workspace is None:
+        workspace = _default_workspace(kind, device, stream)
+    return (workspace, *workspace.get(nbytes, device, stream))
 
 
 def _make_reducer(workspace, group):
@@ -121,9 +137,7 @@ class _DevScalars:
     def __init__(self, lam, rho, device, stream):
         self.lam = self._one(lam, "lambda", device)
         self.rho = self._one(rho, "rho", device)
-        if stream is not None and isinstance(stream, torch.cuda.Stream) and stream != torch.cuda.current_stream(device):
-            for t in (self.lam, self.rho):
-                t.record_stream(stream)
+        _record_streams(stream, device, self.lam, self.rho)
 
     @staticmethod
     def _one(v, name, device):
@@ -179,41 +193,14 @@ def _forward_raw(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, out=Non
           Device tensors are read in-kernel (admm_tvd_forward_dev_f32): no host synchronisation.
     h:    PSF tensor (kw, kh) (Julia (kh,kw,1,1)), or None / empty for the reference's empty PSF.
     Returns a new tensor x of y's shape (y is not modified)."""
-    if not isinstance(y, torch.Tensor) or y.device.type != "cuda":
-        raise TypeError("tvd_fft: y must be a torch tensor on a ROCm device (no CPU path in this package)")
-    if y.dtype != torch.float32:
-        raise TypeError("tvd_fft: y must be float32 (the reference's T)")
-    shape = y.shape
-    if y.dim() == 2:
-        y4 = y.reshape(1, 1, *shape)
-    elif y.dim() == 3:
-        y4 = y.reshape(1, *shape)
-    elif y.dim() == 4:
-        y4 = y
-    else:
-        raise ValueError("tvd_fft: y must be 2-D, 3-D or 4-D")
-    y4 = y4.contiguous()
+    shape, y4, hbuf = _prep(y, h, ranks=(2, 3, 4))
     B, P, N, M = y4.shape
-    if h is None or (isinstance(h, torch.Tensor) and h.numel() == 0):
-        hp, kh, kw, hbuf = None, 0, 0, None
-    else:
-        hbuf = h.detach()
-        while hbuf.dim() > 2 and hbuf.shape[0] == 1:
-            hbuf = hbuf[0]
-        if hbuf.dim() != 2:
-            raise ValueError("PSF must be 2-D (kw, kh)")
-        hbuf = hbuf.to(device=y.device, dtype=torch.float32).contiguous()
-        kw, kh = hbuf.shape
-        hp = hbuf.data_ptr()
-    if out is None:
-        out = torch.empty_like(y4)
-    elif out.shape != y4.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != y.device:
-        raise ValueError("out must be a contiguous float32 tensor of y's shape on y's device")
+    kw, kh = (0, 0) if hbuf is None else hbuf.shape
+    hp = None if hbuf is None else hbuf.data_ptr()
+    out = _out_like(out, y4)
     stream, s_handle = _stream_of(stream, y.device)
-    nbytes = _lib.workspace_bytes(M, N, P, B, kh, kw, isotropic)
-    if workspace is None:
-        workspace = _default_workspace("fwd", y.device, stream)
-    ws_ptr, ws_len = workspace.get(nbytes, y.device, stream)
+    workspace, ws_ptr, ws_len = _acquire("fwd", _lib.workspace_bytes(M, N, P, B, kh, kw, isotropic), y.device, stream,
+                                         workspace)
     red, keep = _make_reducer(workspace, group) if _sharded(isotropic, group) else (None, None)
     if _on_device(lam, rho):
         dv = _DevScalars(lam, rho, y.device, stream)
@@ -232,9 +219,27 @@ def _forward_raw(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, out=Non
     return out.reshape(shape)
 
 
-def _prep(y, h):
+def _check_y(y, who, ranks=None, ranks_text=""):
+    """y of every entry point: a float32 tensor on a ROCm device (the reference's T; this package has no CPU path),
+    of one of the given ranks."""
     if not isinstance(y, torch.Tensor) or y.device.type != "cuda" or y.dtype != torch.float32:
-        raise TypeError("y must be a float32 torch tensor on a ROCm device (no CPU path in this package)")
+        raise TypeError(f"{who}: y must be a float32 torch tensor on a ROCm device (no CPU path in this package)")
+    if ranks is not None and y.dim() not in ranks:
+        raise ValueError(f"{who}: y must be {ranks_text}")
+
+
+def _out_like(out, y4):
+    """The caller's output tensor, checked, or a new one."""
+    if out is None:
+        return torch.empty_like(y4)
+    if out.shape != y4.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != y4.device:
+        raise ValueError("out must be a contiguous float32 tensor of y's shape on y's device")
+    return out
+
+
+def _prep(y, h, ranks=None):
+    """(y's shape, y as contiguous (B, P, N, M), the PSF as a contiguous float32 (kw, kh) on y's device or None)."""
+    _check_y(y, "tvd_fft", ranks, "2-D, 3-D or 4-D")
     shape = y.shape
     y4 = y.reshape((1,) * (4 - y.dim()) + tuple(shape)).contiguous() if y.dim() < 4 else y.contiguous()
     if h is None or h.numel() == 0:
@@ -242,6 +247,8 @@ def _prep(y, h):
     hb = h.detach()
     while hb.dim() > 2 and hb.shape[0] == 1:
         hb = hb[0]
+    if hb.dim() != 2:
+        raise ValueError("PSF must be 2-D (kw, kh)")
     return shape, y4, hb.to(device=y.device, dtype=torch.float32).contiguous()
 
 
@@ -270,9 +277,7 @@ def tvd_fft_backward(y, x_bar, lam, rho=1.0, h=None, isotropic=False, maxit=100,
     stream, s_handle = _stream_of(stream, y.device)
     dv, lam_h, rho_h = _scalars_for(lam, rho, y.device, stream)
     nbytes = _lib.backward_workspace_bytes(M, N, P, B, kh, kw, isotropic, maxit, want_h)
-    if workspace is None:
-        workspace = _default_workspace("bwd", y.device, stream)
-    ws_ptr, ws_len = workspace.get(nbytes, y.device, stream)
+    workspace, ws_ptr, ws_len = _acquire("bwd", nbytes, y.device, stream, workspace)
     x = torch.empty_like(y4)
     y_bar = torch.empty_like(y4) if need_y else None
     h_bar = torch.empty_like(hb) if want_h else None
@@ -320,8 +325,7 @@ def tvd_fft_record(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, need_
     rec.dims = (M, N, P, B, kh, kw)
     rec.flags = (_lib.REC_HBAR if rec.want_h else 0) | (0 if need_rho else _lib.REC_MASKS)
     nbytes = _lib.backward_workspace_bytes(M, N, P, B, kh, kw, isotropic, maxit, rec.flags)
-    rec.workspace = Workspace()
-    ws_ptr, ws_len = rec.workspace.get(nbytes, y.device, stream)
+    rec.workspace, ws_ptr, ws_len = _acquire(None, nbytes, y.device, stream, Workspace())
     x = torch.empty_like(y4)
     red, keep = _make_reducer(rec.workspace, group) if _sharded(isotropic, group) else (None, None)
     head = (y4.data_ptr(), x.data_ptr(), M, N, P, B, None if hb is None else hb.data_ptr(), kh, kw)
@@ -351,8 +355,7 @@ def tvd_fft_backward_recorded(rec, x, x_bar, *, stream=None, need_y=True, need_r
     if not x4.is_contiguous():
         raise ValueError("x must be the recorded forward's (contiguous) output")
     stream, s_handle = _stream_of(stream, y4.device)
-    ws = rec.workspace
-    ws_ptr, ws_len = ws.get(0, y4.device, stream)
+    ws, ws_ptr, ws_len = _acquire(None, 0, y4.device, stream, rec.workspace)
     y_bar = torch.empty_like(y4) if need_y else None
     h_bar = torch.empty_like(hb) if rec.want_h else None
     scal = torch.zeros(2, dtype=torch.float32, device=y4.device)
@@ -363,9 +366,7 @@ def tvd_fft_backward_recorded(rec, x, x_bar, *, stream=None, need_y=True, need_r
             ctypes.byref(red) if red is not None else None)
     L = _lib.load()
     if rec.dv is not None:
-        if isinstance(stream, torch.cuda.Stream) and stream != torch.cuda.current_stream(y4.device):
-            for t in (rec.dv.lam, rec.dv.rho):
-                t.record_stream(stream)
+        _record_streams(stream, y4.device, rec.dv.lam, rec.dv.rho)
         _lib.check(L.admm_tvd_backward_recorded_dev_f32(*head, *rec.dv.ptrs, *tail))
     else:
         _lib.check(L.admm_tvd_backward_recorded_f32(*head, rec.lam, rec.rho, *tail))
@@ -465,10 +466,7 @@ def tvd_fft_grouped(y, lam, rho, h, isotropic=False, maxit=100, *, out=None, wor
     lam, rho: floats, or tensors of 1 or gb * gp elements (group order b * gp + p); they stay on the device.
     isotropic: the batch coupling of the reference is kept over ALL planes, so lam and rho must have one element.
     Not differentiable itself: tvd_fft_grouped_grad is the entry with the grouped adjoint."""
-    if not isinstance(y, torch.Tensor) or y.device.type != "cuda" or y.dtype != torch.float32:
-        raise TypeError("tvd_fft_grouped: y must be a float32 torch tensor on a ROCm device")
-    if y.dim() != 4:
-        raise ValueError("tvd_fft_grouped: y must be 4-D (B, P, N, M)")
+    _check_y(y, "tvd_fft_grouped", (4,), "4-D (B, P, N, M)")
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (y, h, lam, rho)):
         raise NotImplementedError("tvd_fft_grouped is the plain forward: call tvd_fft_grouped_grad for the grouped "
                                   "adjoint under autograd (or detach the inputs)")
@@ -476,15 +474,10 @@ def tvd_fft_grouped(y, lam, rho, h, isotropic=False, maxit=100, *, out=None, wor
     B, P, N, M = y4.shape
     kw, kh = (0, 0) if hbuf is None else hbuf.shape[2:]
     hp = None if hbuf is None else hbuf.data_ptr()
-    if out is None:
-        out = torch.empty_like(y4)
-    elif out.shape != y4.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != y.device:
-        raise ValueError("out must be a contiguous float32 tensor of y's shape on y's device")
+    out = _out_like(out, y4)
     stream, s_handle = _stream_of(stream, y.device)
     nbytes = _lib.grouped_workspace_bytes(M, N, P, B, gb, gp, kh, kw, isotropic)
-    if workspace is None:
-        workspace = _default_workspace("grouped", y.device, stream)
-    ws_ptr, ws_len = workspace.get(nbytes, y.device, stream)
+    workspace, ws_ptr, ws_len = _acquire("grouped", nbytes, y.device, stream, workspace)
     _record_streams(stream, y.device, lt, rt, hbuf)
     _lib.check(_lib.load().admm_tvd_forward_grouped_dev_f32(
         y4.data_ptr(), out.data_ptr(), M, N, P, B, gb, gp, hp, kh, kw, lt.data_ptr(), rt.data_ptr(), nparam,
@@ -492,20 +485,10 @@ def tvd_fft_grouped(y, lam, rho, h, isotropic=False, maxit=100, *, out=None, wor
     return out
 
 
-def _record_streams(stream, device, *tensors):
-    if isinstance(stream, torch.cuda.Stream) and stream != torch.cuda.current_stream(device):
-        for t in tensors:
-            if t is not None:
-                t.record_stream(stream)
-
-
 def _grouped_args(y, lam, rho, h):
     """A grouped call's arguments resolved: (y4, h (gb, gp, kw, kh) on the device or None, lambda and rho as device
     tensors of nparam elements each, nparam, gb, gp).  Nothing is read back to the host."""
-    if not isinstance(y, torch.Tensor) or y.device.type != "cuda" or y.dtype != torch.float32:
-        raise TypeError("tvd_fft_grouped: y must be a float32 torch tensor on a ROCm device")
-    if y.dim() != 4:
-        raise ValueError("tvd_fft_grouped: y must be 4-D (B, P, N, M)")
+    _check_y(y, "tvd_fft_grouped", (4,), "4-D (B, P, N, M)")
     y4 = y.detach().contiguous()
     B, P, N, M = y4.shape
     if h is None:
@@ -550,41 +533,54 @@ class GroupedRecording:
     __slots__ = ("workspace", "y4", "hb", "lt", "rt", "nparam", "gb", "gp", "iso", "maxit", "want_h")
 
 
-def _grouped_call(fn, y4, xb, outs, hb, lt, rt, nparam, gb, gp, iso, maxit, x, ws_ptr, ws_len, s_handle):
-    B, P, N, M = y4.shape
-    kw, kh = (0, 0) if hb is None else hb.shape[2:]
-    _lib.check(fn(y4.data_ptr(), xb.data_ptr(), *[None if t is None else t.data_ptr() for t in outs], M, N, P, B, gb, gp,
-                  None if hb is None else hb.data_ptr(), kh, kw, lt.data_ptr(), rt.data_ptr(), nparam, int(iso), int(maxit),
-                  x.data_ptr(), ws_ptr, ws_len, s_handle))
+def _grouped_adjoint_args(y, lam, rho, h, isotropic, maxit, need_h):
+    """A grouped adjoint call's arguments resolved (_grouped_args) into a GroupedRecording that holds no workspace yet."""
+    g = GroupedRecording()
+    g.y4, g.hb, g.lt, g.rt, g.nparam, g.gb, g.gp = _grouped_args(y, lam, rho, h)
+    g.iso, g.maxit, g.want_h, g.workspace = bool(isotropic), int(maxit), bool(need_h and g.hb is not None), None
+    return g
 
 
-def _grouped_outs(y4, hb, nparam, want_h, need_y, need_rho):
+def _grouped_geometry(g):
+    """(M, N, P, B, gb, gp, h, kh, kw, lambda, rho, nparam, iso, maxit) as the C ABI's grouped entry points take them."""
+    B, P, N, M = g.y4.shape
+    kw, kh = (0, 0) if g.hb is None else g.hb.shape[2:]
+    return (M, N, P, B, g.gb, g.gp, None if g.hb is None else g.hb.data_ptr(), kh, kw, g.lt.data_ptr(), g.rt.data_ptr(),
+            g.nparam, int(g.iso), g.maxit)
+
+
+def _grouped_workspace(g, kind, stream, workspace):
+    geo = _grouped_geometry(g)
+    nbytes = _lib.grouped_backward_workspace_bytes(*geo[:6], *geo[7:9], g.iso, g.maxit, _lib.REC_HBAR if g.want_h else 0)
+    return _acquire(kind, nbytes, g.y4.device, stream, workspace)
+
+
+def _grouped_sweep(fn, g, x, x_bar, ws, stream, need_y, need_rho):
+    """The two adjoint entry points (recorded, combined): (y_bar, h_bar, lam_bar, rho_bar) of g through workspace ws."""
+    y4 = g.y4
+    xb = x_bar.reshape(y4.shape).to(torch.float32).contiguous()
     y_bar = torch.empty_like(y4) if need_y else None
-    h_bar = torch.empty_like(hb) if want_h else None
-    lam_bar = torch.zeros(nparam, dtype=torch.float32, device=y4.device)
-    rho_bar = torch.zeros(nparam, dtype=torch.float32, device=y4.device) if need_rho else None
-    return y_bar, h_bar, lam_bar, rho_bar
+    h_bar = torch.empty_like(g.hb) if g.want_h else None
+    lam_bar = torch.zeros(g.nparam, dtype=torch.float32, device=y4.device)
+    rho_bar = torch.zeros(g.nparam, dtype=torch.float32, device=y4.device) if need_rho else None
+    outs = (y_bar, h_bar, lam_bar, rho_bar)
+    _record_streams(stream, y4.device, g.lt, g.rt, g.hb)
+    _lib.check(fn(y4.data_ptr(), xb.data_ptr(), *[None if t is None else t.data_ptr() for t in outs],
+                  *_grouped_geometry(g), x.data_ptr(), *ws, _stream_handle(stream)))
+    return outs
 
 
 def tvd_fft_grouped_record(y, lam, rho, h, isotropic=False, maxit=100, *, need_h=True, stream=None):
     """tvd_fft_grouped that records its trajectory.  Returns (x, GroupedRecording).  need_h: the replay will be asked
     for h_bar (the dim-2 spectra are then recorded too, by the 2-pass forward)."""
-    y4, hb, lt, rt, nparam, gb, gp = _grouped_args(y, lam, rho, h)
-    B, P, N, M = y4.shape
-    kw, kh = (0, 0) if hb is None else hb.shape[2:]
+    rec = _grouped_adjoint_args(y, lam, rho, h, isotropic, maxit, need_h)
     stream, s_handle = _stream_of(stream, y.device)
-    rec = GroupedRecording()
-    rec.y4, rec.hb, rec.lt, rec.rt, rec.nparam, rec.gb, rec.gp = y4, hb, lt, rt, nparam, gb, gp
-    rec.iso, rec.maxit, rec.want_h = bool(isotropic), int(maxit), bool(need_h and hb is not None)
-    flags = _lib.REC_HBAR if rec.want_h else 0
-    nbytes = _lib.grouped_backward_workspace_bytes(M, N, P, B, gb, gp, kh, kw, isotropic, maxit, flags)
-    rec.workspace = Workspace()
-    ws_ptr, ws_len = rec.workspace.get(nbytes, y.device, stream)
-    _record_streams(stream, y.device, lt, rt, hb)
-    x = torch.empty_like(y4)
+    rec.workspace, ws_ptr, ws_len = _grouped_workspace(rec, None, stream, Workspace())
+    _record_streams(stream, y.device, rec.lt, rec.rt, rec.hb)
+    x = torch.empty_like(rec.y4)
     _lib.check(_lib.load().admm_tvd_forward_grouped_record_dev_f32(
-        y4.data_ptr(), x.data_ptr(), M, N, P, B, gb, gp, None if hb is None else hb.data_ptr(), kh, kw, lt.data_ptr(),
-        rt.data_ptr(), nparam, int(rec.iso), rec.maxit, flags, ws_ptr, ws_len, s_handle))
+        rec.y4.data_ptr(), x.data_ptr(), *_grouped_geometry(rec), _lib.REC_HBAR if rec.want_h else 0, ws_ptr, ws_len,
+        s_handle))
     return x, rec
 
 
@@ -595,17 +591,13 @@ def tvd_fft_grouped_backward_recorded(rec, x, x_bar, *, need_y=True, need_rho=Tr
     recording."""
     if rec.workspace is None:
         raise RuntimeError("recording already consumed")
-    y4 = rec.y4
-    xb = x_bar.reshape(y4.shape).to(torch.float32).contiguous()
-    x4 = x.reshape(y4.shape)
+    x4 = x.reshape(rec.y4.shape)
     if not x4.is_contiguous():
         raise ValueError("x must be the recorded forward's (contiguous) output")
-    stream, s_handle = _stream_of(stream, y4.device)
-    ws_ptr, ws_len = rec.workspace.get(0, y4.device, stream)
-    outs = _grouped_outs(y4, rec.hb, rec.nparam, rec.want_h, need_y, need_rho)
-    _record_streams(stream, y4.device, rec.lt, rec.rt, rec.hb)
-    _grouped_call(_lib.load().admm_tvd_backward_grouped_recorded_dev_f32, y4, xb, outs, rec.hb, rec.lt, rec.rt, rec.nparam,
-                  rec.gb, rec.gp, rec.iso, rec.maxit, x4, ws_ptr, ws_len, s_handle)
+    stream, _ = _stream_of(stream, rec.y4.device)
+    ws = _acquire(None, 0, rec.y4.device, stream, rec.workspace)[1:]
+    outs = _grouped_sweep(_lib.load().admm_tvd_backward_grouped_recorded_dev_f32, rec, x4, x_bar, ws, stream, need_y,
+                          need_rho)
     rec.workspace = None
     return outs
 
@@ -614,23 +606,11 @@ def tvd_fft_grouped_backward(y, x_bar, lam, rho, h, isotropic=False, maxit=100, 
                              need_rho=True, workspace=None, stream=None):
     """The grouped forward and its adjoint in one call.  Returns (x, y_bar, h_bar, lam_bar, rho_bar), shaped as
     tvd_fft_grouped_backward_recorded's."""
-    y4, hb, lt, rt, nparam, gb, gp = _grouped_args(y, lam, rho, h)
-    B, P, N, M = y4.shape
-    kw, kh = (0, 0) if hb is None else hb.shape[2:]
-    xb = x_bar.reshape(y4.shape).to(torch.float32).contiguous()
-    want_h = bool(need_h and hb is not None)
-    stream, s_handle = _stream_of(stream, y.device)
-    nbytes = _lib.grouped_backward_workspace_bytes(M, N, P, B, gb, gp, kh, kw, isotropic, maxit,
-                                                   _lib.REC_HBAR if want_h else 0)
-    if workspace is None:
-        workspace = _default_workspace("grouped_bwd", y.device, stream)
-    ws_ptr, ws_len = workspace.get(nbytes, y.device, stream)
-    x = torch.empty_like(y4)
-    outs = _grouped_outs(y4, hb, nparam, want_h, need_y, need_rho)
-    _record_streams(stream, y.device, lt, rt, hb)
-    _grouped_call(_lib.load().admm_tvd_backward_grouped_dev_f32, y4, xb, outs, hb, lt, rt, nparam, gb, gp, isotropic, maxit,
-                  x, ws_ptr, ws_len, s_handle)
-    return (x, *outs)
+    g = _grouped_adjoint_args(y, lam, rho, h, isotropic, maxit, need_h)
+    stream, _ = _stream_of(stream, y.device)
+    ws = _grouped_workspace(g, "grouped_bwd", stream, workspace)[1:]
+    x = torch.empty_like(g.y4)
+    return (x, *_grouped_sweep(_lib.load().admm_tvd_backward_grouped_dev_f32, g, x, x_bar, ws, stream, need_y, need_rho))
 
 
 class _TvdFFTGroupedFn(torch.autograd.Function):
@@ -716,11 +696,7 @@ def tvd_fft_multi(y, lams, rhos, maxit=100, *, out=None, record=False, need_rho=
     if isotropic:
         flags |= _lib.MULTI_ISO
     nbytes = _lib.multi_workspace_bytes(M, N, P, B, n, maxit, flags)
-    if record:
-        workspace = Workspace()
-    elif workspace is None:
-        workspace = _default_workspace("multi", y.device, stream)
-    ws_ptr, ws_len = workspace.get(nbytes, y.device, stream)
+    workspace, ws_ptr, ws_len = _acquire("multi", nbytes, y.device, stream, Workspace() if record else workspace)
     if out is None:
         out = torch.empty((B, n * P, N, M), dtype=torch.float32, device=y.device)
     elif out.shape != (B, n * P, N, M) or not out.is_contiguous():
@@ -747,7 +723,7 @@ def tvd_fft_multi_backward_recorded(rec, x, x_bar, *, need_y=True, need_rho=True
         raise ValueError("recorded with need_rho=False: rho_bar is not available")
     stream, s_handle = _stream_of(stream, x.device)
     xb = x_bar.reshape(x.shape).to(torch.float32).contiguous()
-    ws_ptr, ws_len = rec.workspace.get(0, x.device, stream)
+    _, ws_ptr, ws_len = _acquire(None, 0, x.device, stream, rec.workspace)
     y_bar = torch.empty((B, P, N, M), dtype=torch.float32, device=x.device) if need_y else None
     scal = torch.zeros(2 * n, dtype=torch.float32, device=x.device)
     _lib.check(_lib.load().admm_tvd_backward_multi_recorded_dev_f32(

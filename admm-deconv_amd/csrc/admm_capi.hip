@@ -5,6 +5,9 @@
 // keeps the recordings registry (a replay must match its recording) and the profiler, and hands the call
 // to the launch sequencing (admm_launch.hip) with the plan of the path table (admm_paths.hip).  Nothing is
 // allocated and nothing synchronises unless the optional profiler is on.
+// Each single or grouped entry point fills a Call (and an adjoint a Grads, capi_internal.hpp) once; below that there is
+// one validation (check_call), one workspace carver (Carver; take_group_tables for the per-group table blocks), one
+// registry (rec_store / rec_forget / rec_take: nothing else locks it) and one adjoint (run_backward) for both families.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -104,14 +107,6 @@ int admm_tvd_workspace_bytes(int M, int N, int P, int B, int kh, int kw, int iso
 
 namespace admm_capi {
 
-int check_common(const float* y, float* x, int maxit) {
-    if (!y || !x) return fail(ADMM_E_INVALID, "y and x_out must be device pointers");
-    if (maxit < 0) return fail(ADMM_E_INVALID, "maxit must be >= 0 (got %d)", maxit);
-    if ((reinterpret_cast<uintptr_t>(y) & 15) || (reinterpret_cast<uintptr_t>(x) & 15))
-        return fail(ADMM_E_INVALID, "y and x_out must be 16-byte aligned");
-    return ADMM_OK;
-}
-
 int check_ws(void* workspace, size_t have, size_t need) {
     if (!workspace || have < need) return fail(ADMM_E_WORKSPACE, "workspace too small: need %zu bytes, got %zu", need, have);
     if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return fail(ADMM_E_WORKSPACE, "workspace must be 256-byte aligned");
@@ -125,12 +120,7 @@ BwdLayout make_bwd_layout(int M, int N, size_t planes, int kh, int kw, int maxit
     b.f = hd.f;
     b.traj_s = hd.traj_s, b.traj_v = hd.traj_v, b.sig = hd.sig, b.sbA = hd.sbA, b.sbB = hd.sbB, b.vsum = hd.vsum;
     b.traj_n = hd.traj_n;
-    size_t off = hd.end;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = align_up(off + bytes);
-        return o;
-    };
+    Carver cv{hd.end};
     const size_t MN = (size_t)M * N;
     const int K = maxit < 1 ? 1 : maxit;
     const bool gen = generic_shape(M, N);
@@ -138,9 +128,9 @@ BwdLayout make_bwd_layout(int M, int N, size_t planes, int kh, int kw, int maxit
     const bool hq = want_h && kh > 0;
     if (iso) {
         const size_t ng = iso_ngroups(planes);
-        b.wbar = take(planes * MN * 4);   // vbar_k handed from ISO_ADJ_A to ISO_ADJ_B
-        b.Rmap = take(MN * 4);
-        b.Rpart = take(ng * MN * 4);
+        b.wbar = cv.take(planes * MN * 4);   // vbar_k handed from ISO_ADJ_A to ISO_ADJ_B
+        b.Rmap = cv.take(MN * 4);
+        b.Rpart = cv.take(ng * MN * 4);
         b.nblk_isoA = (int)(ng * gen_nb(N, T));
         b.nblk_isoR = kIsoAdjRBlocks;
         b.nblk_line = b.nblk_isoA + b.nblk_isoR;
@@ -148,9 +138,9 @@ BwdLayout make_bwd_layout(int M, int N, size_t planes, int kh, int kw, int maxit
     } else {
         b.nblk_line = (int)(planes * gen_nb(N, T));
     }
-    b.rpart = take((size_t)K * b.nblk_line * 2 * 8);
-    b.Qp = hq ? take(planes * (size_t)(M / 2 + 1) * N * 8) : 0;   // fp64 accumulators
-    b.Q = hq ? take((size_t)(M / 2 + 1) * N * 8) : 0;
+    b.rpart = cv.take((size_t)K * b.nblk_line * 2 * 8);
+    b.Qp = hq ? cv.take(planes * (size_t)(M / 2 + 1) * N * 8) : 0;   // fp64 accumulators
+    b.Q = hq ? cv.take((size_t)(M / 2 + 1) * N * 8) : 0;
     b.TY = 1;   // h_bar correlation tile: the largest of 8, 4, 2, 1 lines dividing N
     for (int t = 8; t > 1; t >>= 1)
         if (N % t == 0) {
@@ -158,12 +148,12 @@ BwdLayout make_bwd_layout(int M, int N, size_t planes, int kh, int kw, int maxit
             break;
         }
     b.nblk_corr = (int)(planes * (N / b.TY));
-    b.hpart = kh > 0 ? take((size_t)b.nblk_corr * kh * kw * 8) : 0;
-    b.hcorr = kh > 0 ? take((size_t)kh * kw * 8) : 0;
-    b.hA = hq ? take((size_t)kh * kw * 8) : 0;
-    b.rt = take(2 * 8);
-    b.rtmp = take((size_t)kRedParts * (kh * kw > 2 ? kh * kw : 2) * 8);
-    b.total = off;
+    b.hpart = kh > 0 ? cv.take((size_t)b.nblk_corr * kh * kw * 8) : 0;
+    b.hcorr = kh > 0 ? cv.take((size_t)kh * kw * 8) : 0;
+    b.hA = hq ? cv.take((size_t)kh * kw * 8) : 0;
+    b.rt = cv.take(2 * 8);
+    b.rtmp = cv.take((size_t)kRedParts * (kh * kw > 2 ? kh * kw : 2) * 8);
+    b.total = cv.off;
     return b;
 }
 
@@ -187,29 +177,57 @@ struct RecTag {
     int grouped, gb, gp, nparam;   // a grouped recording (admm_tvd_forward_grouped_record_dev_f32) and its grouping
     bool operator==(const RecTag& o) const { return std::memcmp(this, &o, sizeof(RecTag)) == 0; }
 };
-std::mutex g_rec_mu;
-std::unordered_map<const void*, RecTag> g_rec;
 float g_dummy_scalar = 0.f;   // stands for "device-resident scalars" when a tag is rebuilt without them
 
-RecTag make_tag(int M, int N, int P, int B, int kh, int kw, int iso, int maxit, bool want_h, const admm::ScalarSrc& sc) {
+// the tag of a call: a single solve's has nbr = 1 and grouped = 0, a grouped call's its grouping, a multi-branch
+// recording's its branch count (set by forward_multi / backward_multi) -- no family replays another's recording
+RecTag make_tag(const Call& c, bool want_h, bool masks) {
     RecTag t;
     std::memset(&t, 0, sizeof(t));
-    t.M = M, t.N = N, t.P = P, t.B = B, t.kh = kh, t.kw = kw, t.iso = iso != 0, t.maxit = maxit, t.want_h = want_h;
+    t.M = c.M, t.N = c.N, t.P = c.P, t.B = c.B, t.kh = c.kh, t.kw = c.kw, t.iso = c.iso != 0, t.maxit = c.maxit;
+    t.want_h = want_h, t.masks = masks;
     t.nbr = 1;
-    t.dev_scalars = sc.lam != nullptr;
-    if (!t.dev_scalars) t.lam = sc.lam_v, t.rho = sc.rho_v;
+    t.dev_scalars = c.sc.lam != nullptr;
+    if (!t.dev_scalars) t.lam = c.sc.lam_v, t.rho = c.sc.rho_v;
     for (int i = 0; i < ADMM_OPT_COUNT; ++i) t.opts[i] = opt(i);
+    t.sharded = c.red != nullptr;
+    t.grouped = c.grouped, t.gb = c.gb, t.gp = c.gp, t.nparam = c.nparam;
     return t;
+}
+
+// The registry: these three functions alone lock g_rec_mu and touch g_rec.
+std::mutex g_rec_mu;
+std::unordered_map<const void*, RecTag> g_rec;
+void rec_store(const void* ws, const RecTag& tag) {
+    std::lock_guard<std::mutex> lk(g_rec_mu);
+    g_rec[ws] = tag;
 }
 void rec_forget(const void* ws) {
     std::lock_guard<std::mutex> lk(g_rec_mu);
     g_rec.erase(ws);
 }
+// A replay, under one lock acquisition: `match` is handed the tag recorded for ws (null: none), rebuilds from it the
+// tag this replay must find and compares; the recording is consumed when it returns ADMM_OK, and kept otherwise.
+template <typename Match>
+int rec_take(const void* ws, Match&& match) {
+    std::lock_guard<std::mutex> lk(g_rec_mu);
+    const auto it = g_rec.find(ws);
+    const int rc = match(it == g_rec.end() ? nullptr : &it->second);
+    if (rc == ADMM_OK && it != g_rec.end()) g_rec.erase(it);
+    return rc;
+}
 
+// a single solve's lambda and rho: host values, or device pointers read in-kernel
 int check_lam_rho(float lambda, float rho) {
     if (!std::isfinite(lambda) || !std::isfinite(rho)) return fail(ADMM_E_INVALID, "lambda and rho must be finite");
     return ADMM_OK;
 }
+int check_dev_scalars(const float* lambda, const float* rho) {
+    if (!lambda || !rho) return fail(ADMM_E_INVALID, "lambda and rho must be device pointers");
+    return ADMM_OK;
+}
+admm::ScalarSrc host_sc(float lambda, float rho) { return admm::ScalarSrc{nullptr, nullptr, lambda, rho}; }
+admm::ScalarSrc dev_sc(const float* lambda, const float* rho) { return admm::ScalarSrc{lambda, rho, 0.f, 0.f}; }
 
 // Library streams of the MALL-resident schedule: created once per device, never destroyed (non-blocking; the
 // forward orders them against the caller's stream with events).
@@ -237,35 +255,85 @@ size_t forward_ws_bytes(int M, int N, size_t planes, int kh, bool iso, const Pat
     return cp.streams > 1 ? (size_t)cp.streams * align_up(one) : one;
 }
 
-int forward_impl(const float* y, float* x_out, int M, int N, int P, int B, const float* h, int kh, int kw,
-                 const admm::ScalarSrc& sc, int iso, int maxit, void* workspace, size_t workspace_bytes, void* stream,
-                 const admm_batch_reducer* reducer) {
-    const admm_batch_reducer* red = (iso && reducer && reducer->fn) ? reducer : nullptr;
-    if (h == nullptr) kh = kw = 0;
+// ---- validation: one function for the single and the grouped family, forward (phases = 0) and adjoint ----
+int check_common(const float* y, float* x, int maxit) {
+    if (!y || !x) return fail(ADMM_E_INVALID, "y and x_out must be device pointers");
+    if (maxit < 0) return fail(ADMM_E_INVALID, "maxit must be >= 0 (got %d)", maxit);
+    if ((reinterpret_cast<uintptr_t>(y) & 15) || (reinterpret_cast<uintptr_t>(x) & 15))
+        return fail(ADMM_E_INVALID, "y and x_out must be 16-byte aligned");
+    return ADMM_OK;
+}
+
+// the grouping of a grouped call or workspace query, after its shape
+int check_grouped(int M, int N, int P, int B, int gb, int gp, int kh, int kw, int iso) {
     int rc = check_shape(M, N, P, B, kh, kw, iso);
     if (rc) return rc;
-    rc = check_common(y, x_out, maxit);
+    if ((gb != 1 && gb != B) || (gp != 1 && gp != P))
+        return fail(ADMM_E_INVALID, "grouped solve: gb must be 1 or B, gp 1 or P (gb=%d gp=%d B=%d P=%d)", gb, gp, B, P);
+    if ((size_t)P * B > kChunkPlanes)
+        return fail(ADMM_E_UNSUPPORTED, "grouped solve: at most %zu planes per call", kChunkPlanes);
+    return ADMM_OK;
+}
+
+// phases: 0 = plain forward, else the adjoint's (run_backward); g: the adjoint's gradients (phases & 2: x_bar is read).
+// A grouped recording accepts ADMM_REC_MASKS without honouring it (the full trajectory is recorded, so rho_bar stays
+// available) and refuses unknown flag bits; a single recording's flags only plan.
+int check_call(const Call& c, int phases, const Grads* g, int rec_flags = 0) {
+    int rc = c.grouped ? check_grouped(c.M, c.N, c.P, c.B, c.gb, c.gp, c.kh, c.kw, c.iso)
+                       : check_shape(c.M, c.N, c.P, c.B, c.kh, c.kw, c.iso);
     if (rc) return rc;
-    const size_t planes = (size_t)P * B;
+    if (c.grouped) {
+        const char* who = phases ? "grouped adjoint" : "grouped solve";
+        if (c.kh > 0 && !c.h) return fail(ADMM_E_INVALID, "%s: h is NULL with a %d x %d PSF", who, c.kh, c.kw);
+        if (!c.sc.lam || !c.sc.rho) return fail(ADMM_E_INVALID, "%s: lambda and rho must be device pointers", who);
+        if (c.nparam != 1 && c.nparam != c.groups())
+            return fail(ADMM_E_INVALID, "%s: nparam must be 1 or the group count %d (got %d)", who, c.groups(), c.nparam);
+        if (c.iso && c.nparam > 1)
+            return fail(ADMM_E_UNSUPPORTED, "%s: the isotropic prox is one BT factor map per batch, so it takes one "
+                                            "(lambda, rho) pair (nparam = 1), got %d", who, c.nparam);
+        if (rec_flags & ~(ADMM_REC_HBAR | ADMM_REC_MASKS)) return fail(ADMM_E_INVALID, "%s: unknown rec_flags 0x%x", who, rec_flags);
+    }
+    rc = check_common(c.y, c.x_out, c.maxit);
+    if (rc) return rc;
+    if ((phases & 2) && (reinterpret_cast<uintptr_t>(g->y_bar) & 15))
+        return fail(ADMM_E_INVALID, "y_bar must be a 16-byte aligned device pointer (or NULL: not needed)");
+    if ((phases & 2) && (!g->x_bar || (reinterpret_cast<uintptr_t>(g->x_bar) & 15)))
+        return fail(ADMM_E_INVALID, "x_bar must be a 16-byte aligned device pointer");
+    if (phases && !c.grouped && c.planes() > 65535)
+        return fail(ADMM_E_UNSUPPORTED, "the adjoint takes at most 65535 planes per call (split the batch)");
+    return ADMM_OK;
+}
+
+// a single solve's descriptor: h == NULL is "no PSF"; the reducer acts on the isotropic prox only
+Call single_call(Call c) {
+    if (c.h == nullptr) c.kh = c.kw = 0;
+    c.red = (c.iso && c.red && c.red->fn) ? c.red : nullptr;
+    return c;
+}
+
+int forward_impl(const Call& c) {
+    int rc = check_call(c, 0, nullptr);
+    if (rc) return rc;
+    const int M = c.M, N = c.N;
+    const bool iso = c.iso != 0;
+    const size_t planes = c.planes();
     // a sharded isotropic solve plans without the plane-count rule: every shard must take the same path, since
     // the fused and 2-pass kernels hand the reducer their sum maps in different layouts (lane-native float2 vs
     // natural), and uneven shards can fall on either side of a threshold
-    const PathPlan pl = plan_paths({M, N, iso != 0, kh > 0, ADMM_MODE_FORWARD, 0, false, false, red ? 0 : planes});
-    const ChunkPlan cp = forward_chunks(M, N, planes, iso != 0, pl.fwd);
+    const PathPlan pl = plan_paths({M, N, iso, c.kh > 0, ADMM_MODE_FORWARD, 0, false, false, c.red ? 0 : planes});
+    const ChunkPlan cp = forward_chunks(M, N, planes, iso, pl.fwd);
     const size_t chunk = cp.chunk;   // an isotropic batch is one chunk
-    const Layout lay = make_layout(M, N, chunk, kh > 0, iso != 0);
-    rc = check_ws(workspace, workspace_bytes, forward_ws_bytes(M, N, planes, kh, iso != 0, &pl));
+    const Layout lay = make_layout(M, N, chunk, c.kh > 0, iso);
+    rc = check_ws(c.workspace, c.workspace_bytes, forward_ws_bytes(M, N, planes, c.kh, iso, &pl));
     if (rc) return rc;
-    rec_forget(workspace);   // whatever was recorded there is overwritten now
-    const hipStream_t s0 = reinterpret_cast<hipStream_t>(stream);
-    const size_t MN = (size_t)M * N;
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    rec_forget(c.workspace);   // whatever was recorded there is overwritten now
+    const hipStream_t s0 = reinterpret_cast<hipStream_t>(c.stream);
+    unsigned char* ws = static_cast<unsigned char*>(c.workspace);
     if (cp.streams <= 1) {
         Launcher ln{s0, g_prof.on, {}};
         // the tables (twiddles, C / G, scalars) once: later chunks reuse them from the same workspace
         for (size_t p0 = 0; p0 < planes && rc == 0; p0 += chunk)
-            rc = run_forward(ln, y + p0 * MN, x_out + p0 * MN, M, N, std::min(chunk, planes - p0), h, kh, kw, sc, iso,
-                             maxit, ws, lay, Traj{}, red, pl.fwd, p0 == 0);
+            rc = run_forward(ln, c, ws, lay, Traj{}, pl.fwd, p0 == 0, p0, std::min(chunk, planes - p0));
         int rc2 = ln.finish();
         return rc ? rc : rc2;
     }
@@ -292,8 +360,8 @@ int forward_impl(const float* y, float* x_out, int M, int N, int P, int B, const
     for (size_t p0 = 0; p0 < planes && rc == 0; p0 += chunk, ++i) {
         const int k = (int)(i % (size_t)n);
         // each stream's chunk workspace builds the tables with its first chunk (96 setup launches per c4 solve -> 4)
-        rc = run_forward(lns[k], y + p0 * MN, x_out + p0 * MN, M, N, std::min(chunk, planes - p0), h, kh, kw, sc, iso,
-                         maxit, ws + (size_t)k * stride, lay, Traj{}, red, pl.fwd, i < (size_t)n);
+        rc = run_forward(lns[k], c, ws + (size_t)k * stride, lay, Traj{}, pl.fwd, i < (size_t)n, p0,
+                         std::min(chunk, planes - p0));
     }
     // join: the caller's stream waits for every library stream (also after an error, so nothing is left running
     // against the caller's buffers unordered)
@@ -314,216 +382,120 @@ int forward_impl(const float* y, float* x_out, int M, int N, int P, int B, const
     return rc;
 }
 
-GroupedLayout make_grouped_layout(int M, int N, size_t planes, int groups, bool psf, bool iso) {
-    GroupedLayout L{};
-    L.f = make_layout(M, N, planes, psf, iso);
-    size_t off = align_up(L.f.total);
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = align_up(off + bytes);
-        return o;
-    };
-    const size_t G = (size_t)groups;
-    L.tab_f = (unsigned)(align_up((size_t)(M / 2 + 1) * N * 4) / 4);
-    L.f.prm = take(G * 16);
-    L.f.C = take(G * L.tab_f * 4);
-    L.f.G = psf ? take(G * L.tab_f * 8) : 0;
-    L.f.F = fused_tables_shape(M, N) ? take(G * admm::plane::grouped_tables_bytes()) : 0;
-    L.total = L.f.total = off;
-    return L;
+// the per-group blocks of a grouped layout, behind cv: scalars, 2-pass C / G tables, lane-native tables; f's own
+// slots are renamed to group 0's blocks
+void take_group_tables(Carver& cv, Layout& f, int M, int N, size_t G, bool psf) {
+    const size_t tab_f = group_tab_f(M, N);
+    f.prm = cv.take(G * 16);
+    f.C = cv.take(G * tab_f * 4);
+    f.G = psf ? cv.take(G * tab_f * 8) : 0;
+    f.F = fused_tables_shape(M, N) ? cv.take(G * admm::plane::grouped_tables_bytes()) : 0;
 }
 
-// validation shared by the grouped workspace query and the grouped call
-int check_grouped(int M, int N, int P, int B, int gb, int gp, int kh, int kw, int iso) {
-    int rc = check_shape(M, N, P, B, kh, kw, iso);
-    if (rc) return rc;
-    if ((gb != 1 && gb != B) || (gp != 1 && gp != P))
-        return fail(ADMM_E_INVALID, "grouped solve: gb must be 1 or B, gp 1 or P (gb=%d gp=%d B=%d P=%d)", gb, gp, B, P);
-    if ((size_t)P * B > kChunkPlanes)
-        return fail(ADMM_E_UNSUPPORTED, "grouped solve: at most %zu planes per call", kChunkPlanes);
-    return ADMM_OK;
+Layout make_grouped_layout(int M, int N, size_t planes, int groups, bool psf, bool iso) {
+    Layout f = make_layout(M, N, planes, psf, iso);
+    Carver cv{align_up(f.total)};
+    take_group_tables(cv, f, M, N, (size_t)groups, psf);
+    f.total = cv.off;
+    return f;
 }
 
-int forward_grouped(const float* y, float* x_out, int M, int N, int P, int B, int gb, int gp, const float* h, int kh,
-                    int kw, const float* lambda, const float* rho, int nparam, int iso, int maxit, void* workspace,
-                    size_t workspace_bytes, void* stream) {
-    int rc = check_grouped(M, N, P, B, gb, gp, kh, kw, iso);
+int forward_grouped(const Call& c) {
+    int rc = check_call(c, 0, nullptr);
     if (rc) return rc;
-    const int G = gb * gp;
-    if (kh > 0 && !h) return fail(ADMM_E_INVALID, "grouped solve: h is NULL with a %d x %d PSF", kh, kw);
-    if (!lambda || !rho) return fail(ADMM_E_INVALID, "grouped solve: lambda and rho must be device pointers");
-    if (nparam != 1 && nparam != G)
-        return fail(ADMM_E_INVALID, "grouped solve: nparam must be 1 or the group count %d (got %d)", G, nparam);
-    if (iso && nparam > 1)
-        return fail(ADMM_E_UNSUPPORTED, "grouped solve: the isotropic prox is one BT factor map per batch, so it takes "
-                                        "one (lambda, rho) pair (nparam = 1), got %d", nparam);
-    rc = check_common(y, x_out, maxit);
+    const Layout lay = make_grouped_layout(c.M, c.N, c.planes(), c.groups(), c.kh > 0, c.iso != 0);
+    rc = check_ws(c.workspace, c.workspace_bytes, lay.total);
     if (rc) return rc;
-    const size_t planes = (size_t)P * B;
-    const GroupedLayout L = make_grouped_layout(M, N, planes, G, kh > 0, iso != 0);
-    rc = check_ws(workspace, workspace_bytes, L.total);
-    if (rc) return rc;
-    rec_forget(workspace);
-    const int path = plan_grouped(M, N, iso != 0, planes);
-    const admm::plane::Branches br = admm::plane::grouped_branches(P, B, gb, gp, L.tab_f, nparam > 1 ? 4u : 0u);
-    Launcher ln{reinterpret_cast<hipStream_t>(stream), g_prof.on, {}};
-    rc = run_forward(ln, y, x_out, M, N, planes, h, kh, kw, admm::ScalarSrc{lambda, rho, 0.f, 0.f}, iso, maxit,
-                     static_cast<unsigned char*>(workspace), L.f, Traj{}, nullptr, path, true, &br);
+    rec_forget(c.workspace);
+    Launcher ln{reinterpret_cast<hipStream_t>(c.stream), g_prof.on, {}};
+    rc = run_forward(ln, c, static_cast<unsigned char*>(c.workspace), lay, Traj{},
+                     plan_grouped(c.M, c.N, c.iso != 0, c.planes()));
     const int rc2 = ln.finish();
     return rc ? rc : rc2;
 }
 
-GroupedBwdLayout make_grouped_bwd_layout(int M, int N, int P, int B, int gb, int gp, int nparam, int kh, int kw, int maxit,
-                                         bool want_h, bool iso) {
-    GroupedBwdLayout L{};
-    const size_t planes = (size_t)P * B, G = (size_t)gb * gp, ntaps = (size_t)kh * kw;
-    const bool psf = kh > 0, hq = want_h && psf;
-    L.b = make_bwd_layout(M, N, planes, kh, kw, maxit, want_h, iso);
-    size_t off = align_up(L.b.total);
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = align_up(off + bytes);
-        return o;
-    };
-    // the grouped table blocks, as make_grouped_layout places them
-    L.tab_f = (unsigned)(align_up((size_t)(M / 2 + 1) * N * 4) / 4);
-    L.b.f.prm = take(G * 16);
-    L.b.f.C = take(G * L.tab_f * 4);
-    L.b.f.G = psf ? take(G * L.tab_f * 8) : 0;
-    L.b.f.F = fused_tables_shape(M, N) ? take(G * admm::plane::grouped_tables_bytes()) : 0;
+BwdLayout make_grouped_bwd_layout(const Call& c, bool want_h) {
+    const int M = c.M, N = c.N;
+    const size_t planes = c.planes(), G = (size_t)c.groups(), ntaps = (size_t)c.kh * c.kw;
+    const bool psf = c.kh > 0, hq = want_h && psf, iso = c.iso != 0;
+    BwdLayout b = make_bwd_layout(M, N, planes, c.kh, c.kw, c.maxit, want_h, iso);
+    Carver cv{align_up(b.total)};
+    take_group_tables(cv, b.f, M, N, G, psf);
     // per group: PSF spectrum, Q, the two h_bar terms, the (rho_bar, tau_bar) sums
     const size_t nq = (size_t)(M / 2 + 1) * N;
-    L.b.sig = hq ? take(G * nq * 16) : 0;
-    L.b.Q = hq ? take(G * nq * 8) : 0;
-    L.b.hcorr = psf ? take(G * ntaps * 8) : 0;
-    L.b.hA = hq ? take(G * ntaps * 8) : 0;
-    L.b.rt = take(G * 2 * 8);
+    b.sig = hq ? cv.take(G * nq * 16) : 0;
+    b.Q = hq ? cv.take(G * nq * 8) : 0;
+    b.hcorr = psf ? cv.take(G * ntaps * 8) : 0;
+    b.hA = hq ? cv.take(G * ntaps * 8) : 0;
+    b.rt = cv.take(G * 2 * 8);
     // parts of the group-segmented sums: one (lambda, rho) pair sums every plane's rows, G pairs a group's
-    const int K = maxit < 1 ? 1 : maxit;
+    const int K = c.maxit < 1 ? 1 : c.maxit;
     const size_t ppg = planes / G;
-    L.split_rt = iso ? 1 : group_split((long long)K * (L.b.nblk_line / (long long)planes) * (nparam > 1 ? ppg : planes));
-    L.split_h = psf ? group_split((long long)(N / L.b.TY) * ppg) : 1;
-    const size_t t_rt = (size_t)nparam * L.split_rt * 2, t_h = G * L.split_h * ntaps;
-    L.gtmp = take((t_rt > t_h ? t_rt : t_h) * 8);
-    L.total = L.b.total = off;
-    return L;
+    b.split_rt = iso ? 1 : group_split((long long)K * (b.nblk_line / (long long)planes) * (c.nparam > 1 ? ppg : planes));
+    b.split_h = psf ? group_split((long long)(N / b.TY) * ppg) : 1;
+    const size_t t_rt = (size_t)c.nparam * b.split_rt * 2, t_h = G * b.split_h * ntaps;
+    b.gtmp = cv.take((t_rt > t_h ? t_rt : t_h) * 8);
+    b.total = cv.off;
+    return b;
 }
 
-// The grouped adjoint: phases as run_backward (1 = record, 2 = replay, 3 = both).  Grouping, layouts and validation
-// are the grouped forward's (check_grouped); there is no reducer form.  ADMM_REC_MASKS is accepted and not honoured:
-// the full trajectory is recorded, so rho_bar stays available.
-int run_backward_grouped(int phases, int rec_flags, const float* y, const float* x_bar, float* y_bar, float* h_bar,
-                         float* lambda_bar, float* rho_bar, int M, int N, int P, int B, int gb, int gp, const float* h,
-                         int kh, int kw, const float* lambda, const float* rho, int nparam, int iso, int maxit,
-                         float* x_out, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = check_grouped(M, N, P, B, gb, gp, kh, kw, iso);
+// The adjoint of a single or a grouped call.  phases: 1 = forward recording the trajectory into the workspace (writes
+// x_out), 2 = reverse sweep from a recorded workspace (x_out = that forward's output), 3 = both.  rec_flags
+// (ADMM_REC_*): phase 1 alone records the extra h_bar trajectory only when asked (phase 2 must then be given h_bar).
+// A grouped call has no reducer form; its grouping, layouts and validation are the grouped forward's.
+int run_backward(int phases, int rec_flags, const Call& c, const Grads& g) {
+    int rc = check_call(c, phases, &g, rec_flags);
     if (rc) return rc;
-    const int G = gb * gp;
-    if (kh > 0 && !h) return fail(ADMM_E_INVALID, "grouped adjoint: h is NULL with a %d x %d PSF", kh, kw);
-    if (!lambda || !rho) return fail(ADMM_E_INVALID, "grouped adjoint: lambda and rho must be device pointers");
-    if (nparam != 1 && nparam != G)
-        return fail(ADMM_E_INVALID, "grouped adjoint: nparam must be 1 or the group count %d (got %d)", G, nparam);
-    if (iso && nparam > 1)
-        return fail(ADMM_E_UNSUPPORTED, "grouped adjoint: the isotropic prox is one BT factor map per batch, so it takes "
-                                        "one (lambda, rho) pair (nparam = 1), got %d", nparam);
-    if (rec_flags & ~(ADMM_REC_HBAR | ADMM_REC_MASKS)) return fail(ADMM_E_INVALID, "grouped adjoint: unknown rec_flags 0x%x", rec_flags);
-    rc = check_common(y, x_out, maxit);
-    if (rc) return rc;
-    if ((phases & 2) && (reinterpret_cast<uintptr_t>(y_bar) & 15))
-        return fail(ADMM_E_INVALID, "y_bar must be a 16-byte aligned device pointer (or NULL: not needed)");
-    if ((phases & 2) && (!x_bar || (reinterpret_cast<uintptr_t>(x_bar) & 15)))
-        return fail(ADMM_E_INVALID, "x_bar must be a 16-byte aligned device pointer");
-    const size_t planes = (size_t)P * B;
-    const bool want_h = phases == 1 ? (rec_flags & ADMM_REC_HBAR) != 0 : h_bar != nullptr;
-    const GroupedPlan plan = plan_grouped_adjoint(M, N, iso != 0, kh > 0, planes, want_h);
-    const GroupedBwdLayout gl = make_grouped_bwd_layout(M, N, P, B, gb, gp, nparam, kh, kw, maxit, plan.want_h, iso != 0);
-    rc = check_ws(workspace, workspace_bytes, gl.total);
-    if (rc) return rc;
-    RecTag tag = make_tag(M, N, P, B, kh, kw, iso, maxit, plan.want_h, admm::ScalarSrc{lambda, rho, 0.f, 0.f});
-    tag.grouped = 1, tag.gb = gb, tag.gp = gp, tag.nparam = nparam;
-    {
-        std::lock_guard<std::mutex> lk(g_rec_mu);
-        if (phases == 2) {
-            auto it = g_rec.find(workspace);
-            if (it == g_rec.end())
-                return fail(ADMM_E_INVALID, "workspace holds no recording (admm_tvd_forward_grouped_record_dev_f32 first; a "
-                                            "plain forward on the same workspace overwrites it)");
-            if (!(it->second == tag))
-                return fail(ADMM_E_INVALID, "replay does not match its grouped recording (shape, grouping gb / gp / nparam, "
-                                            "PSF, iso, maxit, h_bar request or library options changed between record and "
-                                            "replay, or the recording is a single solve's)");
-            g_rec.erase(it);
-        } else if (phases == 1) {
-            g_rec[workspace] = tag;
+    const bool iso = c.iso != 0;
+    PathPlan plan;
+    BwdLayout bl;
+    RecTag tag;
+    // plan, lay out, check the workspace, tag.  A replay (phase 2) is planned as the recording it replays was: masks
+    // is the recording's flag (a replay whose options or arguments differ is rejected by its tag below).
+    auto prepare = [&](bool masks) {
+        if (c.grouped) {
+            const bool want_h = phases == 1 ? (rec_flags & ADMM_REC_HBAR) != 0 : g.h_bar != nullptr;
+            plan = plan_grouped_adjoint(c.M, c.N, iso, c.kh > 0, c.planes(), want_h);
+            bl = make_grouped_bwd_layout(c, plan.want_h);
         } else {
-            g_rec.erase(workspace);
+            const int pflags = phases != 2 ? rec_flags : (g.h_bar ? ADMM_REC_HBAR : 0) | (masks ? ADMM_REC_MASKS : 0);
+            // sharded (c.red): no plane-count rule, so that every shard records and sweeps in one layout (forward_impl)
+            plan = plan_paths({c.M, c.N, iso, c.kh > 0, phases == 3 ? ADMM_MODE_BACKWARD : ADMM_MODE_RECORD, pflags,
+                               g.h_bar != nullptr, g.rho_bar != nullptr, c.red ? 0 : c.planes()});
+            bl = make_bwd_layout(c.M, c.N, c.planes(), c.kh, c.kw, c.maxit, plan.want_h, iso, plan.masks && !iso);
         }
+        tag = make_tag(c, plan.want_h, plan.masks);
+        return check_ws(c.workspace, c.workspace_bytes, bl.total);
+    };
+    if (phases != 2) {
+        rc = prepare(false);
+        if (rc) return rc;
+        if (phases == 1) rec_store(c.workspace, tag);
+        else rec_forget(c.workspace);
+        return launch_backward(phases, c, g, plan, bl);
     }
-    return launch_backward_grouped(phases, y, x_bar, y_bar, h_bar, lambda_bar, rho_bar, M, N, P, B, gb, gp, h, kh, kw, lambda,
-                                   rho, nparam, iso, maxit, x_out, workspace, stream, plan, gl);
-}
-
-// phases: 1 = forward recording the trajectory into the workspace (writes x_out), 2 = reverse sweep
-// from a recorded workspace (x_out = that forward's output), 3 = both.  rec_flags (ADMM_REC_*): phase 1 alone
-// records the extra h_bar trajectory only when asked (phase 2 must then be given h_bar).
-int run_backward(int phases, int rec_flags, const float* y, const float* x_bar, float* y_bar, float* h_bar,
-                 float* lambda_bar, float* rho_bar, int M, int N, int P, int B, const float* h, int kh, int kw,
-                 const admm::ScalarSrc& sc, int iso, int maxit, float* x_out, void* workspace, size_t workspace_bytes,
-                 void* stream, const admm_batch_reducer* reducer) {
-    const admm_batch_reducer* red = (iso && reducer && reducer->fn) ? reducer : nullptr;
-    if (h == nullptr) kh = kw = 0;
-    int rc = check_shape(M, N, P, B, kh, kw, iso);
-    if (rc) return rc;
-    rc = check_common(y, x_out, maxit);
-    if (rc) return rc;
-    if ((phases & 2) && (reinterpret_cast<uintptr_t>(y_bar) & 15))
-        return fail(ADMM_E_INVALID, "y_bar must be a 16-byte aligned device pointer (or NULL: not needed)");
-    if ((phases & 2) && (!x_bar || (reinterpret_cast<uintptr_t>(x_bar) & 15)))
-        return fail(ADMM_E_INVALID, "x_bar must be a 16-byte aligned device pointer");
-    const size_t planes = (size_t)P * B;
-    if (planes > 65535) return fail(ADMM_E_UNSUPPORTED, "the adjoint takes at most 65535 planes per call (split the batch)");
-    // the plan (plan_paths): a replay (phase 2) is planned as the recording it replays was (its flags are in
-    // the recording's tag; a replay whose options or arguments differ is rejected below)
-    int pflags = rec_flags;
-    if (phases == 2) {
-        std::lock_guard<std::mutex> lk(g_rec_mu);
-        auto it = g_rec.find(workspace);
-        pflags = (h_bar != nullptr ? ADMM_REC_HBAR : 0) | (it != g_rec.end() && it->second.masks ? ADMM_REC_MASKS : 0);
-    }
-    // sharded (red): no plane-count rule, so that every shard records and sweeps in one layout (forward_impl)
-    const PathPlan plan = plan_paths({M, N, iso != 0, kh > 0, phases == 3 ? ADMM_MODE_BACKWARD : ADMM_MODE_RECORD, pflags,
-                                      h_bar != nullptr, rho_bar != nullptr, red ? 0 : planes});
-    const bool want_h = plan.want_h;
-    const bool ln_traj = plan.ln_traj;
-    const bool use_masks = plan.masks;
-    const bool iso_lane = plan.iso_lane;   // the fused isotropic sweep (no mask bits: s itself is needed)
-    const BwdLayout bl = make_bwd_layout(M, N, planes, kh, kw, maxit, want_h, iso != 0, use_masks && !iso);
-    rc = check_ws(workspace, workspace_bytes, bl.total);
-    if (rc) return rc;
-    RecTag tag = make_tag(M, N, P, B, kh, kw, iso, maxit, want_h, sc);
-    tag.masks = use_masks;
-    tag.sharded = red != nullptr;
-    if (phases == 2) {
-        std::lock_guard<std::mutex> lk(g_rec_mu);
-        auto it = g_rec.find(workspace);
-        if (it == g_rec.end())
-            return fail(ADMM_E_INVALID, "workspace holds no recording (admm_tvd_forward_record_* first; a plain forward "
-                                        "on the same workspace overwrites it)");
-        if (!(it->second == tag))
-            return fail(ADMM_E_INVALID, "replay does not match its recording (shape, PSF, iso, maxit, h_bar request, "
-                                        "lambda / rho, library options or the batch reducer (sharded or not) changed "
-                                        "between record and replay)");
-        if (use_masks && rho_bar)
+    rc = rec_take(c.workspace, [&](const RecTag* rec) -> int {
+        const int r = prepare(rec && rec->masks);
+        if (r) return r;
+        if (!rec)
+            return fail(ADMM_E_INVALID, "workspace holds no recording (%s first; a plain forward on the same workspace "
+                                        "overwrites it)",
+                        c.grouped ? "admm_tvd_forward_grouped_record_dev_f32" : "admm_tvd_forward_record_*");
+        if (!(*rec == tag))
+            return c.grouped
+                       ? fail(ADMM_E_INVALID, "replay does not match its grouped recording (shape, grouping gb / gp / nparam, "
+                                              "PSF, iso, maxit, h_bar request or library options changed between record and "
+                                              "replay, or the recording is a single solve's)")
+                       : fail(ADMM_E_INVALID, "replay does not match its recording (shape, PSF, iso, maxit, h_bar request, "
+                                              "lambda / rho, library options or the batch reducer (sharded or not) changed "
+                                              "between record and replay)");
+        if (plan.masks && g.rho_bar)
             return fail(ADMM_E_INVALID, "recorded with ADMM_REC_MASKS (soft-threshold branches only / the fused isotropic "
                                         "trajectory): rho_bar cannot be formed from it; record without the flag to get rho_bar");
-        g_rec.erase(it);
-    } else {
-        std::lock_guard<std::mutex> lk(g_rec_mu);
-        if (phases == 1) g_rec[workspace] = tag;
-        else g_rec.erase(workspace);
-    }
-    return launch_backward(phases, y, x_bar, y_bar, h_bar, lambda_bar, rho_bar, M, N, planes, h, kh, kw, sc, iso, maxit,
-                           x_out, workspace, stream, red, plan, bl);
+        return ADMM_OK;
+    });
+    if (rc) return rc;
+    return launch_backward(phases, c, g, plan, bl);
 }
 
 size_t multi_C_bytes() { return align_up((size_t)(kMultiM / 2 + 1) * kMultiN * 4); }
@@ -534,20 +506,15 @@ size_t multi_iso_rows(int K) { return (size_t)(K > 1 ? K - 1 : 1) * 512; }
 
 MultiLayout make_multi_layout(size_t planes, int nbr, int maxit, int flags) {
     MultiLayout L{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off = align_up(off + bytes);
-        return o;
-    };
+    Carver cv{0};
     const size_t MN = (size_t)kMultiM * kMultiN;
     const int K = maxit < 1 ? 1 : maxit;
     const bool rec = (flags & ADMM_MULTI_RECORD) != 0, iso = (flags & ADMM_MULTI_ISO) != 0;
     const bool masks = (flags & ADMM_REC_MASKS) != 0 && !iso;
-    L.prm = take((size_t)nbr * 16);
-    L.twM = take(kMultiM * 8);
-    L.twN = take(kMultiN * 8);
-    L.C = take((size_t)nbr * multi_C_bytes());
+    L.prm = cv.take((size_t)nbr * 16);
+    L.twM = cv.take(kMultiM * 8);
+    L.twN = cv.take(kMultiN * 8);
+    L.C = cv.take((size_t)nbr * multi_C_bytes());
     L.two_pass = multi_two_pass(planes, flags);
     if (L.two_pass) {
         // the 2-pass kernels over every branch's planes (admm_launch.hip run_multi_2pass_*)
@@ -562,54 +529,54 @@ MultiLayout make_multi_layout(size_t planes, int nbr, int maxit, int flags) {
             L.rows_b = (int)ppb * (kMultiN / T);
         }
         L.pbs = (size_t)K * L.rows_b * 2;
-        L.spec0 = take(planes * MN * 4);
-        L.spec1 = take(planes * MN * 4);
-        L.hln = take(planes * MN * 4);   // Y_h = F y per grid plane (H^T y in the spectral domain)
+        L.spec0 = cv.take(planes * MN * 4);
+        L.spec1 = cv.take(planes * MN * 4);
+        L.hln = cv.take(planes * MN * 4);   // Y_h = F y per grid plane (H^T y in the spectral domain)
         if (iso) {
-            L.fmap = take((size_t)nbr * MN * 4);
-            L.qpart = take((size_t)nbr * L.ngb * MN * 4);
+            L.fmap = cv.take((size_t)nbr * MN * 4);
+            L.qpart = cv.take((size_t)nbr * L.ngb * MN * 4);
         }
         if (rec) {
-            L.traj = take((size_t)(K > 1 ? K - 1 : 1) * planes * MN * 8);
-            L.sbA = take(planes * MN * 8);
-            L.sbB = take(planes * MN * 8);
-            L.vsum = take(planes * MN * 4);
-            L.part = take((size_t)nbr * L.pbs * 8);
-            L.rt = take((size_t)nbr * 16);
-            L.rtmp = take((size_t)kRedParts * 2 * 8);
+            L.traj = cv.take((size_t)(K > 1 ? K - 1 : 1) * planes * MN * 8);
+            L.sbA = cv.take(planes * MN * 8);
+            L.sbB = cv.take(planes * MN * 8);
+            L.vsum = cv.take(planes * MN * 4);
+            L.part = cv.take((size_t)nbr * L.pbs * 8);
+            L.rt = cv.take((size_t)nbr * 16);
+            L.rtmp = cv.take((size_t)kRedParts * 2 * 8);
             if (iso) {
-                L.nrm = take((size_t)(K > 1 ? K - 1 : 1) * nbr * MN * 4);
-                L.wbar = take(planes * MN * 4);
-                L.rmap = take((size_t)nbr * MN * 4);
-                L.Rpart = take((size_t)nbr * L.ngb * MN * 4);
+                L.nrm = cv.take((size_t)(K > 1 ? K - 1 : 1) * nbr * MN * 4);
+                L.wbar = cv.take(planes * MN * 4);
+                L.rmap = cv.take((size_t)nbr * MN * 4);
+                L.Rpart = cv.take((size_t)nbr * L.ngb * MN * 4);
             }
         } else {
-            L.sA = take(planes * MN * 8);
-            if (!iso) L.sbA = take(planes * MN * 8);   // the anisotropic s ping-pong's second buffer
+            L.sA = cv.take(planes * MN * 8);
+            if (!iso) L.sbA = cv.take(planes * MN * 8);   // the anisotropic s ping-pong's second buffer
         }
-        L.total = off;
+        L.total = cv.off;
         return L;
     }
-    L.F = take((size_t)nbr * multi_F_bytes());
-    L.hln = take(admm::plane::hty_bytes(planes));   // lane-native H^T y at its skewed plane stride
-    L.sln = take(planes * MN * 8);
+    L.F = cv.take((size_t)nbr * multi_F_bytes());
+    L.hln = cv.take(admm::plane::hty_bytes(planes));   // lane-native H^T y at its skewed plane stride
+    L.sln = cv.take(planes * MN * 8);
     if (rec) {
-        L.traj = take((size_t)(K > 1 ? K - 1 : 1) * planes * (masks ? MN / 2 : MN * 8));
-        L.sbar = take(planes * MN * 8);
-        L.vsl = take(planes * MN * 4);
-        L.part = take(iso ? (size_t)nbr * multi_iso_rows(K) * 16 : planes * 16);
-        L.rt = take((size_t)nbr * 16);
-        L.rtmp = take((size_t)kRedParts * 2 * 8);
+        L.traj = cv.take((size_t)(K > 1 ? K - 1 : 1) * planes * (masks ? MN / 2 : MN * 8));
+        L.sbar = cv.take(planes * MN * 8);
+        L.vsl = cv.take(planes * MN * 4);
+        L.part = cv.take(iso ? (size_t)nbr * multi_iso_rows(K) * 16 : planes * 16);
+        L.rt = cv.take((size_t)nbr * 16);
+        L.rtmp = cv.take((size_t)kRedParts * 2 * 8);
     }
     if (iso) {
-        L.fmap = take((size_t)nbr * MN * 4);
-        L.qpart = take(planes * MN * 4);
+        L.fmap = cv.take((size_t)nbr * MN * 4);
+        L.qpart = cv.take(planes * MN * 4);
         if (rec) {
-            L.nrm = take((size_t)(K > 1 ? K - 1 : 1) * nbr * MN * 4);
-            L.rmap = take((size_t)nbr * MN * 4);
+            L.nrm = cv.take((size_t)(K > 1 ? K - 1 : 1) * nbr * MN * 4);
+            L.rmap = cv.take((size_t)nbr * MN * 4);
         }
     }
-    L.total = off;
+    L.total = cv.off;
     return L;
 }
 
@@ -631,6 +598,16 @@ admm::plane::Branches multi_branches(int P, int B, int nbr) {
     return admm::plane::Branches{P * B, nbr, P, (unsigned)(multi_F_bytes() / 4), 4u};
 }
 
+// the tag of a multi-branch recording (every branch's scalars are device-resident: a replay is not given them)
+RecTag multi_tag(int P, int B, int nbr, int iso, int maxit, bool masks) {
+    Call c{};
+    c.M = kMultiM, c.N = kMultiN, c.P = P, c.B = B, c.iso = iso, c.maxit = maxit;
+    c.sc = admm::ScalarSrc{&g_dummy_scalar, &g_dummy_scalar, 0.f, 0.f};
+    RecTag t = make_tag(c, false, masks);
+    t.nbr = nbr;
+    return t;
+}
+
 int forward_multi(const float* y, float* x_out, int M, int N, int P, int B, int nbr, const float* const* lambda,
                   const float* const* rho, int maxit, int flags, void* workspace, size_t workspace_bytes, void* stream) {
     int rc = check_multi(M, N, P, B, nbr, maxit, flags);
@@ -644,17 +621,10 @@ int forward_multi(const float* y, float* x_out, int M, int N, int P, int B, int 
     const MultiLayout L = make_multi_layout(planes, nbr, maxit, flags);
     rc = check_ws(workspace, workspace_bytes, L.total);
     if (rc) return rc;
-    {
-        std::lock_guard<std::mutex> lk(g_rec_mu);
-        g_rec.erase(workspace);
-        if (flags & ADMM_MULTI_RECORD) {
-            const int iso = (flags & ADMM_MULTI_ISO) != 0;
-            RecTag t = make_tag(M, N, P, B, 0, 0, iso, maxit, false, admm::ScalarSrc{lambda[0], rho[0], 0.f, 0.f});
-            t.nbr = nbr;
-            t.masks = (flags & ADMM_REC_MASKS) != 0 || iso;   // no rho_bar from either
-            g_rec[workspace] = t;
-        }
-    }
+    const int iso = (flags & ADMM_MULTI_ISO) != 0;
+    // (masks: no rho_bar from the ST mask bits, nor from the isotropic recording)
+    if (flags & ADMM_MULTI_RECORD) rec_store(workspace, multi_tag(P, B, nbr, iso, maxit, (flags & ADMM_REC_MASKS) != 0 || iso));
+    else rec_forget(workspace);
     return launch_forward_multi(y, x_out, M, N, P, B, nbr, lambda, rho, maxit, flags, workspace, stream, planes, L);
 }
 
@@ -666,26 +636,21 @@ int backward_multi(const float* x_bar, float* y_bar, float* lambda_bar, float* r
         (reinterpret_cast<uintptr_t>(y_bar) & 15))
         return fail(ADMM_E_INVALID, "x_bar, x_out (and y_bar if given) must be 16-byte aligned device pointers");
     int flags = ADMM_MULTI_RECORD;
-    {
-        std::lock_guard<std::mutex> lk(g_rec_mu);
-        auto it = g_rec.find(workspace);
-        if (it == g_rec.end() || it->second.nbr != nbr)
+    rc = rec_take(workspace, [&](const RecTag* rec) -> int {
+        if (!rec || rec->nbr != nbr)
             return fail(ADMM_E_INVALID, "workspace holds no multi-branch recording of %d branches "
                                         "(admm_tvd_forward_multi_dev_f32 with ADMM_MULTI_RECORD first)", nbr);
-        const int iso = it->second.iso;
-        RecTag t = make_tag(M, N, P, B, 0, 0, iso, maxit, false, admm::ScalarSrc{&g_dummy_scalar, &g_dummy_scalar, 0.f, 0.f});
-        t.nbr = nbr;
-        t.masks = it->second.masks;
-        if (iso) flags |= ADMM_MULTI_ISO;
-        if (!(it->second == t))
+        // the recording's prox and masks flag; everything else must be this call's
+        if (!(*rec == multi_tag(P, B, nbr, rec->iso, maxit, rec->masks != 0)))
             return fail(ADMM_E_INVALID, "replay does not match its multi-branch recording (shape, maxit or library "
                                         "options changed)");
-        if (t.masks && rho_bar)
+        if (rec->masks && rho_bar)
             return fail(ADMM_E_INVALID, "recorded with ADMM_REC_MASKS (soft-threshold branches only) or ADMM_MULTI_ISO: "
                                         "rho_bar cannot be formed from it");
-        if (t.masks) flags |= ADMM_REC_MASKS;
-        g_rec.erase(it);
-    }
+        flags |= (rec->iso ? ADMM_MULTI_ISO : 0) | (rec->masks ? ADMM_REC_MASKS : 0);
+        return ADMM_OK;
+    });
+    if (rc) return rc;
     const size_t planes = (size_t)P * B * nbr, ppb = (size_t)P * B, MN = (size_t)M * N;
     const MultiLayout L = make_multi_layout(planes, nbr, maxit, flags);
     rc = check_ws(workspace, workspace_bytes, L.total);
@@ -700,6 +665,10 @@ using namespace admm_capi;
 
 extern "C" {
 
+// The single-solve entry points: scalars checked, then Call / Grads filled in once.
+#define ADMM_SINGLE(sc, x, red) \
+    single_call(Call{y, x, M, N, P, B, h, kh, kw, sc, iso, maxit, workspace, workspace_bytes, stream, red})
+
 int admm_tvd_forward_f32(const float* y, float* x_out, int M, int N, int P, int B, const float* h, int kh, int kw,
                          float lambda, float rho, int iso, int maxit, void* workspace, size_t workspace_bytes,
                          void* stream) {
@@ -710,18 +679,15 @@ int admm_tvd_forward_f32(const float* y, float* x_out, int M, int N, int P, int 
 int admm_tvd_forward_sharded_f32(const float* y, float* x_out, int M, int N, int P, int B, const float* h, int kh,
                                  int kw, float lambda, float rho, int iso, int maxit, void* workspace,
                                  size_t workspace_bytes, void* stream, const admm_batch_reducer* reducer) {
-    int rc = check_lam_rho(lambda, rho);
-    if (rc) return rc;
-    return forward_impl(y, x_out, M, N, P, B, h, kh, kw, admm::ScalarSrc{nullptr, nullptr, lambda, rho}, iso, maxit,
-                        workspace, workspace_bytes, stream, reducer);
+    const int rc = check_lam_rho(lambda, rho);
+    return rc ? rc : forward_impl(ADMM_SINGLE(host_sc(lambda, rho), x_out, reducer));
 }
 
 int admm_tvd_forward_dev_f32(const float* y, float* x_out, int M, int N, int P, int B, const float* h, int kh, int kw,
                              const float* lambda, const float* rho, int iso, int maxit, void* workspace,
                              size_t workspace_bytes, void* stream, const admm_batch_reducer* reducer) {
-    if (!lambda || !rho) return fail(ADMM_E_INVALID, "lambda and rho must be device pointers");
-    return forward_impl(y, x_out, M, N, P, B, h, kh, kw, admm::ScalarSrc{lambda, rho, 0.f, 0.f}, iso, maxit,
-                        workspace, workspace_bytes, stream, reducer);
+    const int rc = check_dev_scalars(lambda, rho);
+    return rc ? rc : forward_impl(ADMM_SINGLE(dev_sc(lambda, rho), x_out, reducer));
 }
 
 int admm_tvd_backward_workspace_bytes(int M, int N, int P, int B, int kh, int kw, int iso, int maxit, int want_hbar,
@@ -748,52 +714,43 @@ int admm_tvd_backward_sharded_f32(const float* y, const float* x_bar, float* y_b
                                   float* rho_bar, int M, int N, int P, int B, const float* h, int kh, int kw,
                                   float lambda, float rho, int iso, int maxit, float* x_out, void* workspace,
                                   size_t workspace_bytes, void* stream, const admm_batch_reducer* reducer) {
-    int rc = check_lam_rho(lambda, rho);
-    if (rc) return rc;
-    return run_backward(3, 0, y, x_bar, y_bar, h_bar, lambda_bar, rho_bar, M, N, P, B, h, kh, kw,
-                        admm::ScalarSrc{nullptr, nullptr, lambda, rho}, iso, maxit, x_out, workspace, workspace_bytes,
-                        stream, reducer);
+    const int rc = check_lam_rho(lambda, rho);
+    return rc ? rc : run_backward(3, 0, ADMM_SINGLE(host_sc(lambda, rho), x_out, reducer),
+                                   Grads{x_bar, y_bar, h_bar, lambda_bar, rho_bar});
 }
 
 int admm_tvd_backward_dev_f32(const float* y, const float* x_bar, float* y_bar, float* h_bar, float* lambda_bar,
                               float* rho_bar, int M, int N, int P, int B, const float* h, int kh, int kw,
                               const float* lambda, const float* rho, int iso, int maxit, float* x_out, void* workspace,
                               size_t workspace_bytes, void* stream, const admm_batch_reducer* reducer) {
-    if (!lambda || !rho) return fail(ADMM_E_INVALID, "lambda and rho must be device pointers");
-    return run_backward(3, 0, y, x_bar, y_bar, h_bar, lambda_bar, rho_bar, M, N, P, B, h, kh, kw,
-                        admm::ScalarSrc{lambda, rho, 0.f, 0.f}, iso, maxit, x_out, workspace, workspace_bytes, stream,
-                        reducer);
+    const int rc = check_dev_scalars(lambda, rho);
+    return rc ? rc : run_backward(3, 0, ADMM_SINGLE(dev_sc(lambda, rho), x_out, reducer),
+                                   Grads{x_bar, y_bar, h_bar, lambda_bar, rho_bar});
 }
 
 int admm_tvd_forward_record_f32(const float* y, float* x_out, int M, int N, int P, int B, const float* h, int kh,
                                 int kw, float lambda, float rho, int iso, int maxit, int want_hbar, void* workspace,
                                 size_t workspace_bytes, void* stream, const admm_batch_reducer* reducer) {
-    int rc = check_lam_rho(lambda, rho);
-    if (rc) return rc;
-    return run_backward(1, want_hbar, y, nullptr, nullptr, nullptr, nullptr, nullptr, M, N, P, B, h, kh, kw,
-                        admm::ScalarSrc{nullptr, nullptr, lambda, rho}, iso, maxit, x_out, workspace, workspace_bytes,
-                        stream, reducer);
+    const int rc = check_lam_rho(lambda, rho);
+    return rc ? rc : run_backward(1, want_hbar, ADMM_SINGLE(host_sc(lambda, rho), x_out, reducer), Grads{});
 }
 
 int admm_tvd_forward_record_dev_f32(const float* y, float* x_out, int M, int N, int P, int B, const float* h, int kh,
                                     int kw, const float* lambda, const float* rho, int iso, int maxit, int want_hbar,
                                     void* workspace, size_t workspace_bytes, void* stream,
                                     const admm_batch_reducer* reducer) {
-    if (!lambda || !rho) return fail(ADMM_E_INVALID, "lambda and rho must be device pointers");
-    return run_backward(1, want_hbar, y, nullptr, nullptr, nullptr, nullptr, nullptr, M, N, P, B, h, kh, kw,
-                        admm::ScalarSrc{lambda, rho, 0.f, 0.f}, iso, maxit, x_out, workspace, workspace_bytes, stream,
-                        reducer);
+    const int rc = check_dev_scalars(lambda, rho);
+    return rc ? rc : run_backward(1, want_hbar, ADMM_SINGLE(dev_sc(lambda, rho), x_out, reducer), Grads{});
 }
 
+// (a replay reads x_out, the recorded forward's output)
 int admm_tvd_backward_recorded_f32(const float* y, const float* x_bar, float* y_bar, float* h_bar, float* lambda_bar,
                                    float* rho_bar, int M, int N, int P, int B, const float* h, int kh, int kw,
                                    float lambda, float rho, int iso, int maxit, const float* x_out, void* workspace,
                                    size_t workspace_bytes, void* stream, const admm_batch_reducer* reducer) {
-    int rc = check_lam_rho(lambda, rho);
-    if (rc) return rc;
-    return run_backward(2, 0, y, x_bar, y_bar, h_bar, lambda_bar, rho_bar, M, N, P, B, h, kh, kw,
-                        admm::ScalarSrc{nullptr, nullptr, lambda, rho}, iso, maxit, const_cast<float*>(x_out),
-                        workspace, workspace_bytes, stream, reducer);
+    const int rc = check_lam_rho(lambda, rho);
+    return rc ? rc : run_backward(2, 0, ADMM_SINGLE(host_sc(lambda, rho), const_cast<float*>(x_out), reducer),
+                                   Grads{x_bar, y_bar, h_bar, lambda_bar, rho_bar});
 }
 
 int admm_tvd_backward_recorded_dev_f32(const float* y, const float* x_bar, float* y_bar, float* h_bar,
@@ -801,11 +758,11 @@ int admm_tvd_backward_recorded_dev_f32(const float* y, const float* x_bar, float
                                        int kh, int kw, const float* lambda, const float* rho, int iso, int maxit,
                                        const float* x_out, void* workspace, size_t workspace_bytes, void* stream,
                                        const admm_batch_reducer* reducer) {
-    if (!lambda || !rho) return fail(ADMM_E_INVALID, "lambda and rho must be device pointers");
-    return run_backward(2, 0, y, x_bar, y_bar, h_bar, lambda_bar, rho_bar, M, N, P, B, h, kh, kw,
-                        admm::ScalarSrc{lambda, rho, 0.f, 0.f}, iso, maxit, const_cast<float*>(x_out), workspace,
-                        workspace_bytes, stream, reducer);
+    const int rc = check_dev_scalars(lambda, rho);
+    return rc ? rc : run_backward(2, 0, ADMM_SINGLE(dev_sc(lambda, rho), const_cast<float*>(x_out), reducer),
+                                   Grads{x_bar, y_bar, h_bar, lambda_bar, rho_bar});
 }
+#undef ADMM_SINGLE
 
 int admm_profile_enable(int on) {
     g_prof.on = on != 0;
@@ -902,11 +859,15 @@ int admm_tvd_grouped_workspace_bytes(int M, int N, int P, int B, int gb, int gp,
     return ADMM_OK;
 }
 
+// The grouped entry points: one Call with the grouping, validated by check_call.
+#define ADMM_GROUPED(x)                                                                                             \
+    Call{y, x, M, N, P, B, h, kh, kw, dev_sc(lambda, rho), iso, maxit, workspace, workspace_bytes, stream, nullptr, \
+         gb, gp, nparam, true}
+
 int admm_tvd_forward_grouped_dev_f32(const float* y, float* x_out, int M, int N, int P, int B, int gb, int gp,
                                      const float* h, int kh, int kw, const float* lambda, const float* rho, int nparam,
                                      int iso, int maxit, void* workspace, size_t workspace_bytes, void* stream) {
-    return forward_grouped(y, x_out, M, N, P, B, gb, gp, h, kh, kw, lambda, rho, nparam, iso, maxit, workspace,
-                           workspace_bytes, stream);
+    return forward_grouped(ADMM_GROUPED(x_out));
 }
 
 int admm_tvd_grouped_backward_workspace_bytes(int M, int N, int P, int B, int gb, int gp, int kh, int kw, int iso,
@@ -915,10 +876,15 @@ int admm_tvd_grouped_backward_workspace_bytes(int M, int N, int P, int B, int gb
     const int rc = check_grouped(M, N, P, B, gb, gp, kh, kw, iso);
     if (rc) return rc;
     if (maxit < 0) return fail(ADMM_E_INVALID, "maxit must be >= 0");
-    // (nparam = G: the larger (rho_bar, tau_bar) partial block; a call with one pair fits too)
-    const GroupedPlan pl = plan_grouped_adjoint(M, N, iso != 0, kh > 0, (size_t)P * B, (rec_flags & ADMM_REC_HBAR) != 0);
-    const size_t a = make_grouped_bwd_layout(M, N, P, B, gb, gp, gb * gp, kh, kw, maxit, pl.want_h, iso != 0).total;
-    const size_t b = make_grouped_bwd_layout(M, N, P, B, gb, gp, 1, kh, kw, maxit, pl.want_h, iso != 0).total;
+    const PathPlan pl = plan_grouped_adjoint(M, N, iso != 0, kh > 0, (size_t)P * B, (rec_flags & ADMM_REC_HBAR) != 0);
+    // the larger of a pair per group (the larger (rho_bar, tau_bar) partial block) and one pair (more rows per part)
+    Call c{};
+    c.M = M, c.N = N, c.P = P, c.B = B, c.gb = gb, c.gp = gp, c.kh = kh, c.kw = kw, c.iso = iso, c.maxit = maxit;
+    c.grouped = true;
+    c.nparam = gb * gp;
+    const size_t a = make_grouped_bwd_layout(c, pl.want_h).total;
+    c.nparam = 1;
+    const size_t b = make_grouped_bwd_layout(c, pl.want_h).total;
     *out_bytes = a > b ? a : b;
     return ADMM_OK;
 }
@@ -927,8 +893,7 @@ int admm_tvd_forward_grouped_record_dev_f32(const float* y, float* x_out, int M,
                                             const float* h, int kh, int kw, const float* lambda, const float* rho,
                                             int nparam, int iso, int maxit, int rec_flags, void* workspace,
                                             size_t workspace_bytes, void* stream) {
-    return run_backward_grouped(1, rec_flags, y, nullptr, nullptr, nullptr, nullptr, nullptr, M, N, P, B, gb, gp, h, kh,
-                                kw, lambda, rho, nparam, iso, maxit, x_out, workspace, workspace_bytes, stream);
+    return run_backward(1, rec_flags, ADMM_GROUPED(x_out), Grads{});
 }
 
 int admm_tvd_backward_grouped_recorded_dev_f32(const float* y, const float* x_bar, float* y_bar, float* h_bar,
@@ -936,17 +901,16 @@ int admm_tvd_backward_grouped_recorded_dev_f32(const float* y, const float* x_ba
                                                int gp, const float* h, int kh, int kw, const float* lambda,
                                                const float* rho, int nparam, int iso, int maxit, const float* x_out,
                                                void* workspace, size_t workspace_bytes, void* stream) {
-    return run_backward_grouped(2, 0, y, x_bar, y_bar, h_bar, lambda_bar, rho_bar, M, N, P, B, gb, gp, h, kh, kw, lambda,
-                                rho, nparam, iso, maxit, const_cast<float*>(x_out), workspace, workspace_bytes, stream);
+    return run_backward(2, 0, ADMM_GROUPED(const_cast<float*>(x_out)), Grads{x_bar, y_bar, h_bar, lambda_bar, rho_bar});
 }
 
 int admm_tvd_backward_grouped_dev_f32(const float* y, const float* x_bar, float* y_bar, float* h_bar, float* lambda_bar,
                                       float* rho_bar, int M, int N, int P, int B, int gb, int gp, const float* h, int kh,
                                       int kw, const float* lambda, const float* rho, int nparam, int iso, int maxit,
                                       float* x_out, void* workspace, size_t workspace_bytes, void* stream) {
-    return run_backward_grouped(3, 0, y, x_bar, y_bar, h_bar, lambda_bar, rho_bar, M, N, P, B, gb, gp, h, kh, kw, lambda,
-                                rho, nparam, iso, maxit, x_out, workspace, workspace_bytes, stream);
+    return run_backward(3, 0, ADMM_GROUPED(x_out), Grads{x_bar, y_bar, h_bar, lambda_bar, rho_bar});
 }
+#undef ADMM_GROUPED
 
 int admm_tvd_multi_workspace_bytes(int M, int N, int P, int B, int nbranch, int maxit, int flags, size_t* out_bytes) {
     if (!out_bytes) return fail(ADMM_E_INVALID, "out_bytes is NULL");

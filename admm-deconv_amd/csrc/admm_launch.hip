@@ -8,10 +8,13 @@
 //     two_pass_forward   PREP (Y_h = F(H^T y): line transform, column x conj(Sigma_c), ops.jl:71-81), K x COLUMN,
 //                        (K-1) x LINE (or ISO_A, norm, ISO_B), 1 x FINAL                        (ops.jl:166-174)
 //     two_pass_reverse   line transform of x_bar, then per step COLUMN and the line adjoint (or ISO_ADJ_A, _R, _B)
-//   run_forward          SETUP (twiddles + C, ops.jl:22-37), then the fused / CU-resident / 2-pass path
+//   run_forward          a Call's planes (all, or one chunk): SETUP (twiddles + C, ops.jl:22-37; a grouped call's per
+//                        group), then the fused / CU-resident / 2-pass path
 //   run_forward_generic  the runtime-length path (its own kernels: a separate inverse, the smooth-length alternatives)
-//   launch_backward      recording forward, one reverse sweep (fused, fused isotropic, runtime-length, 2-pass), assembly
+//   launch_backward      the one adjoint driver of single and grouped calls: recording forward, one reverse sweep (fused,
+//                        fused isotropic, runtime-length, 2-pass), assembly; grouping enters through Grouping only
 //   launch_*_multi       the one-grid multi-branch solve: the fused kernels, or the same TwoPass sequences
+// A call arrives as the Call / Grads descriptors of capi_internal.hpp, never as a positional parameter list.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -578,20 +581,37 @@ int fused_iso_forward(Launcher& ln, const FusedIso& f, const float* y, float* x_
     return ADMM_OK;
 }
 
-int run_forward_generic(Launcher& ln, const float* y, float* x_out, int M, int N, size_t planes, const FwdView& v,
-                        int iso, int maxit, const Traj& tr, const admm_batch_reducer* red, int path, const Branches& br);
+// the planes of a call that one run_forward solves: all of them, or a chunk
+struct PlaneRange {
+    const float* y;
+    float* x_out;
+    size_t planes;
+};
+int run_forward_generic(Launcher& ln, const Call& c, const PlaneRange& r, const FwdView& v, const Traj& tr, int path,
+                        const Branches& br);
 
-int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t planes, const float* h, int kh,
-                int kw, const admm::ScalarSrc& sc, int iso, int maxit, unsigned char* ws, const Layout& lay,
-                const Traj& tr, const admm_batch_reducer* red, int fwd_path, bool tables, const Branches* grp) {
+// a grouped call's descriptor for the 2-pass / runtime-length kernels (C / G tables group_tab_f apart, a scalar block per
+// group when it has a (lambda, rho) pair per group); a single solve: kOneSolve
+Branches call_branches(const Call& c) {
+    if (!c.grouped) return kOneSolve;
+    return admm::plane::grouped_branches(c.P, c.B, c.gb, c.gp, group_tab_f(c.M, c.N), c.nparam > 1 ? 4u : 0u);
+}
+
+int run_forward(Launcher& ln, const Call& c, unsigned char* ws, const Layout& lay, const Traj& tr, int fwd_path,
+                bool tables, size_t p0, size_t np) {
     hipStream_t s = ln.s;
     int rc = ADMM_OK;
-    const size_t MN = (size_t)M * N;
+    const int M = c.M, N = c.N, kh = c.kh, kw = c.kw, iso = c.iso, maxit = c.maxit;
+    const size_t MN = (size_t)M * N, planes = np ? np : c.planes();
+    const float* y = c.y + p0 * MN;
+    float* x_out = c.x_out + p0 * MN;
+    const float* h = c.h;
+    const admm::ScalarSrc& sc = c.sc;
+    const admm_batch_reducer* red = c.red;
     const FwdView v = view(ws, lay, kh > 0);
     const int L = M / 2;
-
-    // a grouped solve: the 2-pass / runtime-length kernels' descriptor (C / G tables tab_f apart)
-    const Branches br = grp ? *grp : kOneSolve;
+    const bool grp = c.grouped;
+    const Branches br = call_branches(c);
     if (tables) rc = ln.run(ADMM_K_SETUP, [&] {
         const size_t lds = (size_t)(M + N) * 16 + (kh * kw <= admm::kSetupPsfLds ? (size_t)kh * kw * 4 : 0);
         const int nb = (int)(((size_t)(L + 1) * N * (kh > 0 ? admm::kSetupSplit : 1) + kThreads - 1) / kThreads);
@@ -620,7 +640,7 @@ int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t
 
     const int path = fwd_path;
     if (generic_shape(M, N)) {   // ADMM_PATH_RESIDENT (smooth sides), _SMOOTH, _RUNTIME: the runtime-length layout
-        return run_forward_generic(ln, y, x_out, M, N, planes, v, iso, maxit, tr, red, path, br);
+        return run_forward_generic(ln, c, PlaneRange{y, x_out, planes}, v, tr, path, br);
     }
     if (path == ADMM_PATH_FUSED) {
         // one workgroup per plane runs all K iterations (plane_kernel.hip); lane-native H^T y in
@@ -654,14 +674,14 @@ int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t
                          reinterpret_cast<float2*>(v.fmap), v.spec1};
         return fused_iso_forward(ln, f, y, x_out, kh > 0, v.spec0, maxit, red, reinterpret_cast<float2*>(v.part));
     }
-    const TwoPass c = two_pass_single(ln, M, N, planes, line_T(M, N), v, br);
+    const TwoPass t = two_pass_single(ln, M, N, planes, line_T(M, N), v, br);
     if (path == ADMM_PATH_RESIDENT || path == ADMM_PATH_RESIDENT_ISO) {
         // power-of-two sides admm_resident.hip compiled: one workgroup per plane runs all K iterations (s_k into
         // the trajectory slots when recording, natural layout, as the 2-pass sweep reads them); H^T y from the
         // 2-pass kernels (line, column x conj(Sigma_c), line), the first line spectrum formed in the kernel
         float* hty = kh > 0 ? v.hty : const_cast<float*>(y);
         if (kh > 0) {
-            rc = two_pass_conv(c, ADMM_K_PREP, 1, y, hty);
+            rc = two_pass_conv(t, ADMM_K_PREP, 1, y, hty);
             if (rc) return rc;
         }
         if (path == ADMM_PATH_RESIDENT_ISO) return run_resident_iso(ln, M, N, planes, v, hty, x_out, maxit, tr, red);
@@ -670,7 +690,7 @@ int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t
                                     v.prm, maxit);
         });
     }
-    return two_pass_forward(c, y, x_out, maxit, iso != 0, tr, v.s[0], iso ? v.s[0] : v.s[1], red);
+    return two_pass_forward(t, y, x_out, maxit, iso != 0, tr, v.s[0], iso ? v.s[0] : v.s[1], red);
 }
 
 // ---- the runtime-length kernels (admm_generic.hip, admm_generic_bwd.hip) -----------------------------------
@@ -733,11 +753,16 @@ int gen_conv(Launcher& ln, const GenPass& p, const FwdView& v, int cls, int mode
     return gen_line_inv(ln, p, v, cls, v.spec1, dst);
 }
 
-int run_forward_generic(Launcher& ln, const float* y, float* x_out, int M, int N, size_t planes, const FwdView& v,
-                        int iso, int maxit, const Traj& tr, const admm_batch_reducer* red, int path, const Branches& br) {
+int run_forward_generic(Launcher& ln, const Call& c, const PlaneRange& r, const FwdView& v, const Traj& tr, int path,
+                        const Branches& br) {
     namespace g = admm::gen;
     hipStream_t s = ln.s;
     int rc = ADMM_OK;
+    const int M = c.M, N = c.N, iso = c.iso, maxit = c.maxit;
+    const float* y = r.y;
+    float* x_out = r.x_out;
+    const size_t planes = r.planes;
+    const admm_batch_reducer* red = c.red;
     const size_t MN = (size_t)M * N;
     // (a grouped solve runs the runtime-length kernels only: they take the group offsets)
     const GenPass p = gen_pass(M, N, planes, opt(ADMM_OPT_SMOOTH) != 0 && br.nbr != 0);
@@ -1109,81 +1134,137 @@ int branch_grads(Launcher& ln, const MultiView& v, size_t bstride, int rows, flo
         if (e_ != hipSuccess) return fail(ADMM_E_HIP, "%s: %s", #call, hipGetErrorString(e_));         \
     } while (0)
 
-// Assembly of a single solve's gradients: the (rho_bar, tau_bar) rows, y_bar = H Vsum (or Vsum), h_bar = the
-// correlation of Vsum with y and the spectral term from Q, then lambda_bar / rho_bar / h_bar.
+// group-segmented column sums of partial rows [step][plane][blk] x w -> out[group][w] (reduce_groups_kernel)
+void launch_reduce_groups(hipStream_t s, const double* part, double* out, int nsteps, size_t step_rows, int nblk, int w,
+                          const Branches& br, int groups, int split, double* tmp) {
+    const long long n = ((long long)nsteps * admm::group_planes(br) * nblk + split - 1) / split;
+    const int nt = n <= 64 ? 64 : kThreads;
+    hipLaunchKernelGGL(admm::reduce_groups_kernel, dim3(w, groups, split), dim3(nt), 0, s, part, split > 1 ? tmp : out,
+                       nsteps, step_rows, nblk, w, br);
+    if (split > 1)
+        hipLaunchKernelGGL(admm::reduce_groups_fin_kernel, dim3((groups * w + 255) / 256), dim3(256), 0, s, tmp, out, split,
+                           w, groups * w);
+}
+
+// How grouping enters the adjoint driver, consulted where a grouped call differs from a single solve: the kernels'
+// descriptor, G PSF groups, nparam (lambda, rho) pairs and the parts the group-segmented sums are split in.  A single
+// solve is kOneSolve with one group; a grouped call with one group still runs the grouped kernels.  The workspace of
+// a grouped call is a BwdLayout whose table, scalar, sig, Q, hcorr, hA and rt slots are the per-group blocks
+// (make_grouped_bwd_layout).
+struct Grouping {
+    Branches br;
+    int G, nparam;
+    unsigned tab_f;
+    int split_rt, split_h;
+    double* gtmp;
+    bool on() const { return br.nbr == 0; }
+};
+Grouping grouping_of(const Call& c, const BwdLayout& bl, unsigned char* ws) {
+    if (!c.grouped) return Grouping{kOneSolve, 1, 1, 0u, 1, 1, nullptr};
+    return Grouping{call_branches(c), c.groups(), c.nparam, group_tab_f(c.M, c.N), bl.split_rt, bl.split_h,
+                    at<double>(ws, bl.gtmp)};
+}
+
+// Assembly of the gradients: the (rho_bar, tau_bar) rows, y_bar = H Vsum (or Vsum), h_bar = the correlation of Vsum
+// with y and the spectral term from Q, then lambda_bar / rho_bar / h_bar -- per group for a grouped call (every plane
+// with its group's tables; admm_backward.hip, last section).
 // conv: the path's spectral convolution (two_pass_conv or gen_conv) of Vsum into y_bar; copy: y_bar is not already
 // Vsum (the fused sweeps write it there)
 template <typename Conv>
-int assemble_grads(Launcher& ln, const BwdView& v, const BwdLayout& bl, const float* y, float* y_bar, float* h_bar,
-                   float* lambda_bar, float* rho_bar, int M, int N, size_t planes, int kh, int kw, int red_rows, bool copy,
-                   Conv&& conv) {
+int assemble_grads(Launcher& ln, const BwdView& v, const BwdLayout& bl, const Call& c, const Grads& g, const Grouping& gr,
+                   int red_rows, bool copy, Conv&& conv) {
     hipStream_t s = ln.s;
     const SweepBufs& b = v.b;
-    int rc = ln.run(ADMM_K_FINAL, [&] { launch_reduce_cols(s, b.part, v.rt, red_rows, 2, v.rtmp); });
+    const int M = c.M, N = c.N, kh = c.kh, kw = c.kw, ntaps = kh * kw;
+    const size_t planes = c.planes();
+    // (rho_bar, tau_bar): every row into one pair -- or, anisotropic grouped, per (lambda, rho) pair its planes' rows
+    const Branches all{c.P * c.B, 0, c.P, 0u, 0u, 0, 0};   // one pair for every group: one segment of all planes
+    int rc = ln.run(ADMM_K_FINAL, [&] {
+        if (!gr.on() || c.iso) launch_reduce_cols(s, b.part, v.rt, red_rows, 2, v.rtmp);
+        else launch_reduce_groups(s, b.part, v.rt, c.maxit, (size_t)bl.nblk_line, bl.nblk_line / (int)planes, 2,
+                                  gr.nparam > 1 ? gr.br : all, gr.nparam, gr.split_rt, gr.gtmp);
+    });
     if (rc) return rc;
     if (kh > 0 && b.vsum) {
-        if (y_bar) {   // y_bar = H vsum  (centred circular convolution, spectrally)
-            rc = conv(b.vsum, y_bar);
+        if (g.y_bar) {   // y_bar = H vsum  (centred circular convolution, spectrally; a plane's own group's H)
+            rc = conv(b.vsum, g.y_bar);
             if (rc) return rc;
         }
-        if (h_bar) {
+        if (g.h_bar) {
             rc = ln.run(ADMM_K_FINAL, [&] {
                 const size_t lds = (size_t)(2 * bl.TY + kw - 1) * M * 4;
                 set_lds(admm::hbar_corr_kernel, lds);
                 hipLaunchKernelGGL(admm::hbar_corr_kernel, dim3(N / bl.TY, (unsigned)planes), dim3(kThreads), lds, s,
-                                   b.vsum, y, v.hpart, M, N, kh, kw, bl.TY);
+                                   b.vsum, c.y, v.hpart, M, N, kh, kw, bl.TY);
             });
             if (rc) return rc;
-            rc = ln.run(ADMM_K_FINAL, [&] { launch_reduce_cols(s, v.hpart, v.hcorr, bl.nblk_corr, kh * kw, v.rtmp); });
+            rc = ln.run(ADMM_K_FINAL, [&] {
+                if (!gr.on()) launch_reduce_cols(s, v.hpart, v.hcorr, bl.nblk_corr, ntaps, v.rtmp);
+                else launch_reduce_groups(s, v.hpart, v.hcorr, 1, 0, N / bl.TY, ntaps, gr.br, gr.G, gr.split_h, gr.gtmp);
+            });
             if (rc) return rc;
             const int nq = (M / 2 + 1) * N;
             rc = ln.run(ADMM_K_FINAL, [&] {
-                hipLaunchKernelGGL(admm::reduce_planes_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, b.Qp, v.Q,
-                                   (int)planes, nq);
+                if (!gr.on())
+                    hipLaunchKernelGGL(admm::reduce_planes_kernel, dim3((nq + 255) / 256), dim3(256), 0, s, b.Qp, v.Q,
+                                       (int)planes, nq);
+                else
+                    hipLaunchKernelGGL(admm::reduce_planes_grouped_kernel, dim3((nq + 255) / 256, (unsigned)gr.G), dim3(256),
+                                       0, s, b.Qp, v.Q, nq, gr.br);
             });
             if (rc) return rc;
             rc = ln.run(ADMM_K_FINAL, [&] {
-                hipLaunchKernelGGL(admm::hbarA_kernel, dim3(kh * kw), dim3(kThreads), 0, s, v.Q, v.f.C, v.sig, kh, M, N, v.hA);
+                if (!gr.on())
+                    hipLaunchKernelGGL(admm::hbarA_kernel, dim3(ntaps), dim3(kThreads), 0, s, v.Q, v.f.C, v.sig, kh, M, N, v.hA);
+                else
+                    hipLaunchKernelGGL(admm::hbarA_grouped_kernel, dim3(ntaps, (unsigned)gr.G), dim3(kThreads), 0, s, v.Q,
+                                       v.f.C, v.sig, kh, ntaps, M, N, v.hA, gr.tab_f);
             });
             if (rc) return rc;
         }
-    } else if (copy && y_bar) {
-        HIPCHK(hipMemcpyAsync(y_bar, b.vsum, planes * (size_t)M * N * 4, hipMemcpyDeviceToDevice, s));
+    } else if (copy && g.y_bar) {
+        HIPCHK(hipMemcpyAsync(g.y_bar, b.vsum, planes * (size_t)M * N * 4, hipMemcpyDeviceToDevice, s));
     }
     return ln.run(ADMM_K_FINAL, [&] {
-        const int nt = kh * kw > 1 ? kh * kw : 1;
-        hipLaunchKernelGGL(admm::grads_final_kernel, dim3((nt + 255) / 256), dim3(256), 0, s, v.rt, v.hcorr, v.hA, kh * kw,
-                           v.f.prm, lambda_bar, rho_bar, (h_bar && kh > 0) ? h_bar : nullptr);
+        const int nt = ntaps > 1 ? ntaps : 1;
+        const bool hb = g.h_bar && kh > 0;
+        if (!gr.on())
+            hipLaunchKernelGGL(admm::grads_final_kernel, dim3((nt + 255) / 256), dim3(256), 0, s, v.rt, v.hcorr, v.hA, ntaps,
+                               v.f.prm, g.lambda_bar, g.rho_bar, hb ? g.h_bar : nullptr);
+        else
+            hipLaunchKernelGGL(admm::grads_final_grouped_kernel, dim3((nt + 255) / 256, (unsigned)gr.G), dim3(256), 0, s,
+                               v.rt, hb ? v.hcorr : nullptr, hb ? v.hA : nullptr, ntaps, v.f.prm, gr.br.prm_f, gr.nparam,
+                               g.lambda_bar, g.rho_bar, hb ? g.h_bar : nullptr);
     });
 }
 
-int launch_backward(int phases, const float* y, const float* x_bar, float* y_bar, float* h_bar, float* lambda_bar,
-                    float* rho_bar, int M, int N, size_t planes, const float* h, int kh, int kw,
-                    const admm::ScalarSrc& sc, int iso, int maxit, float* x_out, void* workspace, void* stream,
-                    const admm_batch_reducer* red, const PathPlan& plan, const BwdLayout& bl) {
+// The adjoint of a single or a grouped call: one recording forward, one reverse sweep over every plane (a grouped
+// call's with its group's tables and scalars; plan: plan_paths or plan_grouped_adjoint), then the assembly.
+int launch_backward(int phases, const Call& c, const Grads& g, const PathPlan& plan, const BwdLayout& bl) {
     int rc = ADMM_OK;
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    unsigned char* ws = static_cast<unsigned char*>(c.workspace);
+    hipStream_t s = reinterpret_cast<hipStream_t>(c.stream);
     Launcher ln{s, g_prof.on, {}};
-    const size_t MN = (size_t)M * N;
-    const int K = maxit;
-    if (!x_out || (reinterpret_cast<uintptr_t>(x_out) & 15))
-        return fail(ADMM_E_INVALID, "x_out (forward output of the recomputed solve) must be a 16-byte aligned device pointer");
+    const int M = c.M, N = c.N, kh = c.kh, K = c.maxit;
+    const bool iso = c.iso != 0;
+    const size_t planes = c.planes(), MN = (size_t)M * N;
+    const Grouping gr = grouping_of(c, bl, ws);
     if (K == 0) {
         if (phases & 2) {
-            if (y_bar) HIPCHK(hipMemsetAsync(y_bar, 0, planes * MN * 4, s));
-            if (h_bar && kh > 0) HIPCHK(hipMemsetAsync(h_bar, 0, (size_t)kh * kw * 4, s));
-            if (lambda_bar) HIPCHK(hipMemsetAsync(lambda_bar, 0, 4, s));
-            if (rho_bar) HIPCHK(hipMemsetAsync(rho_bar, 0, 4, s));
+            if (g.y_bar) HIPCHK(hipMemsetAsync(g.y_bar, 0, planes * MN * 4, s));
+            if (g.h_bar && kh > 0) HIPCHK(hipMemsetAsync(g.h_bar, 0, (size_t)gr.G * kh * c.kw * 4, s));
+            if (g.lambda_bar) HIPCHK(hipMemsetAsync(g.lambda_bar, 0, (size_t)gr.nparam * 4, s));
+            if (g.rho_bar) HIPCHK(hipMemsetAsync(g.rho_bar, 0, (size_t)gr.nparam * 4, s));
         }
-        if (phases & 1) HIPCHK(hipMemsetAsync(x_out, 0, planes * MN * 4, s));
+        if (phases & 1) HIPCHK(hipMemsetAsync(c.x_out, 0, planes * MN * 4, s));
         return ln.finish();
     }
     // Vsum = sum_k vbar_k feeds y_bar and the h_bar correlation only: without either the sweeps skip it
-    const bool want_v = y_bar != nullptr || (h_bar != nullptr && kh > 0);
-    const BwdView v = view(ws, bl, kh > 0, iso != 0, plan.want_h, want_v, rho_bar ? x_out : nullptr);
+    const bool want_v = g.y_bar != nullptr || (g.h_bar != nullptr && kh > 0);
+    const BwdView v = view(ws, bl, kh > 0, iso, plan.want_h, want_v, g.rho_bar ? c.x_out : nullptr);
     const SweepBufs& b = v.b;
-    // ---- forward with trajectory ----
+    // ---- forward with trajectory (s_k natural or, from the fused kernel, lane-native; with h_bar the dim-2 spectra
+    // and the PSF spectrum, a grouped call's of every group) ----
     Traj tr;
     tr.s = const_cast<float*>(b.traj);
     tr.m = plan.masks && !iso ? at<unsigned>(ws, bl.traj_s) : nullptr;
@@ -1192,16 +1273,16 @@ int launch_backward(int phases, const float* y, const float* x_bar, float* y_bar
     tr.sig = v.sig;
     tr.nrm = const_cast<float*>(b.nrm);
     if (phases & 1) {
-        rc = run_forward(ln, y, x_out, M, N, planes, h, kh, kw, sc, iso, K, ws, bl.f, tr, red, plan.fwd);
+        rc = run_forward(ln, c, ws, bl.f, tr, plan.fwd);
         if (rc) return rc;
     }
     if (!(phases & 2)) return ln.finish();
-    // replay (phase 2 alone): the recording's {tau, rho, lambda} block is still in the workspace and is
-    // used as is -- the reverse sweep must differentiate the trajectory that was recorded, even if a
-    // device-resident lambda / rho has changed since (host values were checked against the tag above)
+    // replay (phase 2 alone): the recording's tables and {tau, rho, lambda} blocks are still in the workspace and are
+    // used as they are -- the reverse sweep must differentiate the trajectory that was recorded, even if a
+    // device-resident lambda / rho has changed since (host values were checked against the tag)
     // ---- reverse sweep ----
-    // the fused sweeps write Vsum straight into y_bar without a PSF
-    float* vout = !want_v ? nullptr : kh > 0 ? b.vsum : y_bar;
+    // the fused sweeps (single solves only) write Vsum straight into y_bar without a PSF
+    float* vout = !want_v ? nullptr : kh > 0 ? b.vsum : g.y_bar;
     const bool fused = plan.bwd == ADMM_PATH_SWEEP_FUSED || plan.bwd == ADMM_PATH_SWEEP_FUSED_ISO;
     int red_rows = K * bl.nblk_line;   // rows of (rho_bar, tau_bar) partials
     if (!fused) {
@@ -1211,15 +1292,15 @@ int launch_backward(int phases, const float* y, const float* x_bar, float* y_bar
         if (b.Qp) HIPCHK(hipMemsetAsync(b.Qp, 0, planes * (size_t)(M / 2 + 1) * N * 8, s));
     }
     const bool gen = generic_shape(M, N);   // runtime-length path (admm_generic.hip, admm_generic_bwd.hip)
-    const GenPass gp = gen ? gen_pass(M, N, planes, false) : GenPass{};
+    const GenPass gpass = gen ? gen_pass(M, N, planes, false) : GenPass{};
     auto grid = [&] {   // the 2-pass grid of the sweep and of y_bar = H Vsum (power-of-two shapes)
-        TwoPass c = two_pass_single(ln, M, N, planes, bwd_line_T(M, N, iso != 0), v.f);
-        c.rows = bl.nblk_line, c.r_off = bl.nblk_isoA;
-        return c;
+        TwoPass t = two_pass_single(ln, M, N, planes, bwd_line_T(M, N, iso), v.f, gr.br);
+        t.rows = bl.nblk_line, t.r_off = bl.nblk_isoA;
+        return t;
     };
     switch (plan.bwd) {
         case ADMM_PATH_SWEEP_FUSED:   // D x_K in the second sbar buffer, lane-native Vsum in spec0
-            rc = fused_reverse(ln, x_bar, v.f.F, b.traj, tr.m != nullptr, b.xK, reinterpret_cast<float4*>(b.sb[1]),
+            rc = fused_reverse(ln, g.x_bar, v.f.F, b.traj, tr.m != nullptr, b.xK, reinterpret_cast<float4*>(b.sb[1]),
                                reinterpret_cast<float4*>(b.sb[0]), v.f.spec0, vout, b.part, v.f.prm, K, planes);
             red_rows = (int)planes;
             break;
@@ -1231,24 +1312,23 @@ int launch_backward(int phases, const float* y, const float* x_bar, float* y_bar
             HIPCHK(hipMemsetAsync(b.part, 0, (size_t)red_rows * 2 * 8, s));
             const FusedIso f{v.f.F, v.f.prm, planes, nullptr, reinterpret_cast<float4*>(tr.s), planes * kE,
                              reinterpret_cast<float2*>(tr.nrm), kE, nullptr, v.f.spec1};
-            rc = fused_iso_reverse(ln, f, x_bar, at<float2>(ws, bl.wbar), reinterpret_cast<float4*>(b.sb[0]),
-                                   at<float2>(ws, bl.Rmap), v.f.spec0, vout, b.part, 0, K, red);
+            rc = fused_iso_reverse(ln, f, g.x_bar, at<float2>(ws, bl.wbar), reinterpret_cast<float4*>(b.sb[0]),
+                                   at<float2>(ws, bl.Rmap), v.f.spec0, vout, b.part, 0, K, c.red);
             break;
         }
         case ADMM_PATH_SWEEP_RUNTIME:
         case ADMM_PATH_SWEEP_RUNTIME_ISO:
-            rc = runtime_reverse(ln, gp, v.f, b, x_bar, x_out, K, iso != 0, bl.nblk_line, bl.nblk_isoA, red);
+            rc = runtime_reverse(ln, gpass, v.f, b, g.x_bar, c.x_out, K, iso, bl.nblk_line, bl.nblk_isoA, c.red, gr.br);
             break;
         default:
-            rc = two_pass_reverse(grid(), b, x_bar, K, iso != 0, plan.ln_traj, red);
+            rc = two_pass_reverse(grid(), b, g.x_bar, K, iso, plan.ln_traj, c.red);
     }
     if (rc) return rc;
     // ---- assembly ----
-    rc = assemble_grads(ln, v, bl, y, y_bar, h_bar, lambda_bar, rho_bar, M, N, planes, kh, kw, red_rows, !fused,
-                        [&](const float* src, float* dst) {
-                            return gen ? gen_conv(ln, gp, v.f, ADMM_K_FINAL, 2, src, dst)
-                                       : two_pass_conv(grid(), ADMM_K_FINAL, 2, src, dst);
-                        });
+    rc = assemble_grads(ln, v, bl, c, g, gr, red_rows, !fused, [&](const float* src, float* dst) {
+        return gen ? gen_conv(ln, gpass, v.f, ADMM_K_FINAL, 2, src, dst, gr.br)
+                   : two_pass_conv(grid(), ADMM_K_FINAL, 2, src, dst, gr.br);
+    });
     if (rc) return rc;
     return ln.finish();
 }
@@ -1372,128 +1452,6 @@ int launch_backward_multi(const float* x_bar, float* y_bar, float* lambda_bar, f
     return ln.finish();
 }
 
-// ---- grouped adjoint (admm_tvd_backward_grouped_*) ---------------------------------------------------------------
-// One recorded forward and one reverse sweep over every plane, each with its group's tables and scalars (plan:
-// admm_paths.hip plan_grouped_adjoint), then the per-group assembly (admm_backward.hip, last section).  The workspace
-// is a BwdLayout whose table, scalar, sig, Q, hcorr, hA and rt slots are the per-group blocks (GroupedBwdLayout).
-
-// group-segmented column sums of partial rows [step][plane][blk] x w -> out[group][w] (reduce_groups_kernel)
-void launch_reduce_groups(hipStream_t s, const double* part, double* out, int nsteps, size_t step_rows, int nblk, int w,
-                          const Branches& br, int groups, int split, double* tmp) {
-    const long long n = ((long long)nsteps * admm::group_planes(br) * nblk + split - 1) / split;
-    const int nt = n <= 64 ? 64 : kThreads;
-    hipLaunchKernelGGL(admm::reduce_groups_kernel, dim3(w, groups, split), dim3(nt), 0, s, part, split > 1 ? tmp : out,
-                       nsteps, step_rows, nblk, w, br);
-    if (split > 1)
-        hipLaunchKernelGGL(admm::reduce_groups_fin_kernel, dim3((groups * w + 255) / 256), dim3(256), 0, s, tmp, out, split,
-                           w, groups * w);
-}
-
-int launch_backward_grouped(int phases, const float* y, const float* x_bar, float* y_bar, float* h_bar,
-                            float* lambda_bar, float* rho_bar, int M, int N, int P, int B, int gb, int gp, const float* h,
-                            int kh, int kw, const float* lambda, const float* rho, int nparam, int iso, int maxit,
-                            float* x_out, void* workspace, void* stream, const GroupedPlan& plan,
-                            const GroupedBwdLayout& gl) {
-    int rc = ADMM_OK;
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    Launcher ln{s, g_prof.on, {}};
-    const size_t planes = (size_t)P * B, MN = (size_t)M * N;
-    const int K = maxit, G = gb * gp, ntaps = kh * kw;
-    const BwdLayout& bl = gl.b;
-    if (K == 0) {
-        if (phases & 2) {
-            if (y_bar) HIPCHK(hipMemsetAsync(y_bar, 0, planes * MN * 4, s));
-            if (h_bar && kh > 0) HIPCHK(hipMemsetAsync(h_bar, 0, (size_t)G * ntaps * 4, s));
-            if (lambda_bar) HIPCHK(hipMemsetAsync(lambda_bar, 0, (size_t)nparam * 4, s));
-            if (rho_bar) HIPCHK(hipMemsetAsync(rho_bar, 0, (size_t)nparam * 4, s));
-        }
-        if (phases & 1) HIPCHK(hipMemsetAsync(x_out, 0, planes * MN * 4, s));
-        return ln.finish();
-    }
-    const Branches br = admm::plane::grouped_branches(P, B, gb, gp, gl.tab_f, nparam > 1 ? 4u : 0u);
-    const bool want_v = y_bar != nullptr || (h_bar != nullptr && kh > 0);
-    const BwdView v = view(ws, bl, kh > 0, iso != 0, plan.want_h, want_v, rho_bar ? x_out : nullptr);
-    const SweepBufs& b = v.b;
-    // ---- forward with trajectory (s_k natural or, from the fused kernel, lane-native; with h_bar the dim-2 spectra
-    // and every group's PSF spectrum) ----
-    Traj tr;
-    tr.s = const_cast<float*>(b.traj);
-    tr.v = b.v;
-    tr.sig = v.sig;
-    tr.nrm = const_cast<float*>(b.nrm);
-    if (phases & 1) {
-        rc = run_forward(ln, y, x_out, M, N, planes, h, kh, kw, admm::ScalarSrc{lambda, rho, 0.f, 0.f}, iso, K, ws, bl.f, tr,
-                         nullptr, plan.fwd, true, &br);
-        if (rc) return rc;
-    }
-    if (!(phases & 2)) return ln.finish();
-    // ---- reverse sweep: the replay uses the tables and scalar blocks the recording left in the workspace ----
-    if (b.vsum) HIPCHK(hipMemsetAsync(b.vsum, 0, planes * MN * 4, s));
-    if (iso) HIPCHK(hipMemsetAsync(b.part, 0, (size_t)K * bl.nblk_line * 2 * 8, s));   // k = 1: no ISO_ADJ_R rows
-    if (b.Qp) HIPCHK(hipMemsetAsync(b.Qp, 0, planes * (size_t)(M / 2 + 1) * N * 8, s));
-    const bool gen = generic_shape(M, N);
-    const GenPass gpass = gen ? gen_pass(M, N, planes, false) : GenPass{};
-    auto grid = [&] {
-        TwoPass c = two_pass_single(ln, M, N, planes, bwd_line_T(M, N, iso != 0), v.f, br);
-        c.rows = bl.nblk_line, c.r_off = bl.nblk_isoA;
-        return c;
-    };
-    if (gen) rc = runtime_reverse(ln, gpass, v.f, b, x_bar, x_out, K, iso != 0, bl.nblk_line, bl.nblk_isoA, nullptr, br);
-    else rc = two_pass_reverse(grid(), b, x_bar, K, iso != 0, plan.ln_traj);
-    if (rc) return rc;
-    // ---- assembly ----
-    // (rho_bar, tau_bar): isotropic -- one pair, every row; anisotropic -- per (lambda, rho) group, its planes' rows
-    const Branches all{P * B, 0, P, 0u, 0u, 0, 0};   // one pair for every group: one segment of all planes
-    rc = ln.run(ADMM_K_FINAL, [&] {
-        if (iso) launch_reduce_cols(s, b.part, v.rt, K * bl.nblk_line, 2, v.rtmp);
-        else launch_reduce_groups(s, b.part, v.rt, K, (size_t)bl.nblk_line, bl.nblk_line / (int)planes, 2,
-                                  nparam > 1 ? br : all, nparam, gl.split_rt, at<double>(ws, gl.gtmp));
-    });
-    if (rc) return rc;
-    if (kh > 0 && b.vsum) {
-        if (y_bar) {   // y_bar = H_g Vsum: every plane with its group's G table
-            rc = gen ? gen_conv(ln, gpass, v.f, ADMM_K_FINAL, 2, b.vsum, y_bar, br)
-                     : two_pass_conv(grid(), ADMM_K_FINAL, 2, b.vsum, y_bar, br);
-            if (rc) return rc;
-        }
-        if (h_bar) {
-            rc = ln.run(ADMM_K_FINAL, [&] {
-                const size_t lds = (size_t)(2 * bl.TY + kw - 1) * M * 4;
-                set_lds(admm::hbar_corr_kernel, lds);
-                hipLaunchKernelGGL(admm::hbar_corr_kernel, dim3(N / bl.TY, (unsigned)planes), dim3(kThreads), lds, s,
-                                   b.vsum, y, v.hpart, M, N, kh, kw, bl.TY);
-            });
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_FINAL, [&] {
-                launch_reduce_groups(s, v.hpart, v.hcorr, 1, 0, N / bl.TY, ntaps, br, G, gl.split_h, at<double>(ws, gl.gtmp));
-            });
-            if (rc) return rc;
-            const int nq = (M / 2 + 1) * N;
-            rc = ln.run(ADMM_K_FINAL, [&] {
-                hipLaunchKernelGGL(admm::reduce_planes_grouped_kernel, dim3((nq + 255) / 256, (unsigned)G), dim3(256), 0, s,
-                                   b.Qp, v.Q, nq, br);
-            });
-            if (rc) return rc;
-            rc = ln.run(ADMM_K_FINAL, [&] {
-                hipLaunchKernelGGL(admm::hbarA_grouped_kernel, dim3(ntaps, (unsigned)G), dim3(kThreads), 0, s, v.Q, v.f.C,
-                                   v.sig, kh, ntaps, M, N, v.hA, gl.tab_f);
-            });
-            if (rc) return rc;
-        }
-    } else if (y_bar) {
-        HIPCHK(hipMemcpyAsync(y_bar, b.vsum, planes * MN * 4, hipMemcpyDeviceToDevice, s));
-    }
-    rc = ln.run(ADMM_K_FINAL, [&] {
-        const int nt = ntaps > 1 ? ntaps : 1;
-        const bool hb = h_bar && kh > 0;
-        hipLaunchKernelGGL(admm::grads_final_grouped_kernel, dim3((nt + 255) / 256, (unsigned)G), dim3(256), 0, s, v.rt,
-                           hb ? v.hcorr : nullptr, hb ? v.hA : nullptr, ntaps, v.f.prm, br.prm_f, nparam, lambda_bar,
-                           rho_bar, hb ? h_bar : nullptr);
-    });
-    if (rc) return rc;
-    return ln.finish();
-}
 #undef HIPCHK
 
 // ---- the grouped adjoint's instantiations of the 2-pass kernels (last: see "template dispatch" above) ----

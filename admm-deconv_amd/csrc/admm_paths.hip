@@ -214,11 +214,11 @@ int plan_grouped(int M, int N, bool iso, size_t planes) {
     return iso ? ADMM_PATH_2PASS_ISO : ADMM_PATH_2PASS;
 }
 
-// Grouped adjoint: the recording forward and the reverse sweep of a grouped call (capi_internal.hpp GroupedPlan).  The
+// Grouped adjoint: the recording forward and the reverse sweep of a grouped call (masks and iso_lane stay false).  The
 // fused forward records s only (no dim-2 spectra), so a recording for h_bar takes the 2-pass forward; the sweep is
 // always the 2-pass / runtime-length one, whose kernels take the plane -> group map.
-GroupedPlan plan_grouped_adjoint(int M, int N, bool iso, bool psf, size_t planes, bool want_h) {
-    GroupedPlan pl;
+PathPlan plan_grouped_adjoint(int M, int N, bool iso, bool psf, size_t planes, bool want_h) {
+    PathPlan pl;
     pl.want_h = want_h && psf;
     if (generic_shape(M, N)) {
         pl.fwd = ADMM_PATH_RUNTIME;
@@ -335,7 +335,7 @@ int admm_query_grouped_paths(int M, int N, int iso, int kh, long long planes, in
         return ADMM_OK;
     }
     const bool want_h = mode == ADMM_MODE_RECORD ? (flags & ADMM_REC_HBAR) != 0 : want_hbar != 0;
-    const GroupedPlan pl = plan_grouped_adjoint(M, N, iso != 0, kh > 0, (size_t)planes, want_h);
+    const PathPlan pl = plan_grouped_adjoint(M, N, iso != 0, kh > 0, (size_t)planes, want_h);
     *fwd_path = pl.fwd;
     *bwd_path = pl.bwd;
     return ADMM_OK;

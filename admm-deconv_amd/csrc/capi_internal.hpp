@@ -3,7 +3,9 @@
 //                   queries, the recordings registry, the profiler API, the output transport (copy / IPC)
 //   admm_paths.hip  the path decision table (plan_paths), the library options and the tile-size policy
 //   admm_launch.hip launch sequencing of the 2-pass / runtime-length / CU-resident / fused paths (the only TU
-//                   that includes the 2-pass kernels): one 2-pass forward and one reverse sweep for every caller
+//                   that includes the 2-pass kernels): one 2-pass forward and one reverse sweep for every caller,
+//                   one adjoint driver for single and grouped calls
+// A single or grouped call crosses these layers as one Call (and one Grads) by const reference.
 // Reference interface: tvd_fft / tvd_fft_gpu, /root/reference/src/ops/ops.jl:99-188.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -148,8 +150,7 @@ struct Traj {
     bool iso_lane = false;   // isotropic 256 x 256: s and nrm lane-native (plane_iso.hip), for the fused adjoint
 };
 
-// ---- path selection (admm_paths.hip) ----
-// ---- path selection: ONE decision table for every entry point -----------------------------------------------
+// ---- path selection (admm_paths.hip): ONE decision table for every entry point -----------------------------------------------
 // Which kernels a call runs is decided here and nowhere else; run_forward / run_forward_generic / run_backward
 // only execute the plan, and admm_query_paths (include/admm_deconv.h) returns it to tests without a GPU.
 // Inputs: shape, prox, PSF, what the call is (plain forward, recording with ADMM_REC_* flags, combined
@@ -186,6 +187,10 @@ struct BwdLayout {
     size_t rtmp;                        // two-stage column sums (kRedParts x columns doubles)
     int nblk_line, nblk_corr, TY;
     int nblk_isoA, nblk_isoR;           // isotropic: per-step partial rows = nblk_isoA + nblk_isoR
+    // a grouped call (make_grouped_bwd_layout), zero otherwise: the split partials of the group-segmented sums and the
+    // parts a group's (rho_bar, tau_bar) rows / h_bar correlation rows are summed in
+    size_t gtmp;
+    int split_rt, split_h;
 };
 
 constexpr int kIsoAdjRBlocks = 256;     // ISO_ADJ_R grid (tau_bar partial rows per step)
@@ -219,73 +224,86 @@ size_t multi_F_bytes();
 size_t multi_iso_rows(int K);
 admm::plane::Branches multi_branches(int P, int B, int nbr);
 
+// ---- the call descriptor ----
+// What a solve is.  Every extern "C" entry point of the single and the grouped family fills one in once, and
+// everything below the ABI receives it by const reference.
+struct Call {
+    const float* y;
+    float* x_out;
+    int M, N, P, B;
+    const float* h;           // a grouped call: one PSF per group, consecutive
+    int kh, kw;
+    admm::ScalarSrc sc;       // a grouped call: lam / rho point at nparam device values
+    int iso, maxit;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+    const admm_batch_reducer* red;   // the batch reducer, only where it acts: isotropic and fn set
+    int gb = 1, gp = 1, nparam = 1;  // the grouping (admm_tvd_*_grouped_*); a single solve: one group, one pair
+    bool grouped = false;
+    size_t planes() const { return (size_t)P * B; }
+    int groups() const { return gb * gp; }
+};
+// What an adjoint reads (x_bar) and writes (null: not wanted); all null for a recording forward.
+struct Grads {
+    const float* x_bar;
+    float *y_bar, *h_bar, *lambda_bar, *rho_bar;
+};
+
+// ---- workspace carving ----
+struct Carver {
+    size_t off;
+    size_t take(size_t bytes) {
+        const size_t o = off;
+        off = align_up(off + bytes);
+        return o;
+    }
+};
+
 // ---- grouped solve (admm_tvd_forward_grouped_dev_f32) ----
 // One path decision (admm_paths.hip): the fused kernel at 256 x 256 anisotropic from the plane-count rule, the
 // 2-pass kernels at the other tuned shapes, the runtime-length kernels elsewhere (never the smooth-length, resident
 // or fused isotropic kernels, never the MALL chunk schedule).
 int plan_grouped(int M, int N, bool iso, size_t planes);
+// floats (C) / float2 (G) between the groups' 2-pass tables
+inline unsigned group_tab_f(int M, int N) { return (unsigned)(align_up((size_t)(M / 2 + 1) * N * 4) / 4); }
 // Workspace: the single-PSF forward layout of the whole batch, and behind it G consecutive blocks of each table
-// (tab_f floats of C, tab_f float2 of G and grouped_tables_bytes() of lane-native tables per group; one 16-byte scalar
-// block per group).  The layout's own scalar / C / G / lane-native slots stay allocated and are not used (one table
-// set, about 0.8 MB at 256 x 256); `f` names the appended blocks instead.
-struct GroupedLayout {
-    Layout f;          // prm, C, G, F point at group 0's blocks
-    unsigned tab_f;    // floats (C) / float2 (G) between the groups' 2-pass tables
-    size_t total;
-};
-GroupedLayout make_grouped_layout(int M, int N, size_t planes, int groups, bool psf, bool iso);
+// (group_tab_f floats of C, as many float2 of G and grouped_tables_bytes() of lane-native tables per group; one 16-byte
+// scalar block per group).  The layout's own scalar / C / G / lane-native slots stay allocated and are not used (one
+// table set, about 0.8 MB at 256 x 256); prm, C, G and F name group 0's appended blocks instead.
+Layout make_grouped_layout(int M, int N, size_t planes, int groups, bool psf, bool iso);
 
 // ---- grouped adjoint (admm_tvd_backward_grouped_*) ----
 // One path decision (admm_paths.hip), reported by admm_query_grouped_paths: runtime-length shapes record with the
 // runtime-length forward and sweep with sweep_runtime(_iso); 256 x 256 anisotropic from the plane-count rule, fused
 // enabled and no h_bar trajectory records lane-native s with the fused forward and sweeps with sweep_2pass (ln_traj);
 // everything else is the 2-pass forward and sweep_2pass(_iso).  Never the fused reverse sweeps (one table set), the
-// smooth-length or resident kernels, or the MALL chunk schedule.
-struct GroupedPlan {
-    int fwd = 0, bwd = 0;    // ADMM_PATH_* / ADMM_PATH_SWEEP_*
-    bool want_h = false;     // the dim-2 spectra and the groups' PSF spectra are recorded (h_bar)
-    bool ln_traj = false;    // the fused forward records s lane-native
-};
-GroupedPlan plan_grouped_adjoint(int M, int N, bool iso, bool psf, size_t planes, bool want_h);
-// Workspace: a BwdLayout of the whole batch, behind it the grouped table blocks of GroupedLayout and, per group, sig
-// (PSF spectrum), Q, hcorr, hA and rt; b.f.prm / C / G / F and b.sig / Q / hcorr / hA / rt name those blocks (the
+// smooth-length or resident kernels, or the MALL chunk schedule: masks and iso_lane stay false.
+PathPlan plan_grouped_adjoint(int M, int N, bool iso, bool psf, size_t planes, bool want_h);
+// Workspace: a BwdLayout of the whole batch, behind it the grouped table blocks of make_grouped_layout and, per group,
+// sig (PSF spectrum), Q, hcorr, hA and rt; f.prm / C / G / F and sig / Q / hcorr / hA / rt name those blocks (the
 // layout's own single-set slots stay allocated and unused).  gtmp: the split partials of the group-segmented sums.
-struct GroupedBwdLayout {
-    BwdLayout b;
-    unsigned tab_f;
-    size_t gtmp, total;
-    int split_rt, split_h;   // parts a group's (rho_bar, tau_bar) rows / h_bar correlation rows are summed in
-};
-GroupedBwdLayout make_grouped_bwd_layout(int M, int N, int P, int B, int gb, int gp, int nparam, int kh, int kw, int maxit,
-                                         bool want_h, bool iso);
+BwdLayout make_grouped_bwd_layout(const Call& c, bool want_h);
 // parts for a fixed-order sum of n rows: about 4096 rows per block, at most 256 parts
 inline int group_split(long long n) {
     const long long p = (n + 4095) / 4096;
     return p < 1 ? 1 : p > 256 ? 256 : (int)p;
 }
-int launch_backward_grouped(int phases, const float* y, const float* x_bar, float* y_bar, float* h_bar,
-                            float* lambda_bar, float* rho_bar, int M, int N, int P, int B, int gb, int gp, const float* h,
-                            int kh, int kw, const float* lambda, const float* rho, int nparam, int iso, int maxit,
-                            float* x_out, void* workspace, void* stream, const GroupedPlan& plan,
-                            const GroupedBwdLayout& gl);
 
 // ---- launch sequencing (admm_launch.hip) ----
-// The four entry points below set a call up and pick its path; the 2-pass kernels' step sequences exist once
-// (two_pass_forward / two_pass_reverse on a TwoPass grid: a single or grouped solve, or the one-grid call's
-// branches), as do the isotropic norm step, the fused isotropic loops and the per-branch gradient assembly.
-// grp (run_forward): a grouped solve -- h holds one PSF per group, sc.lam / sc.rho point at nparam device values
-// (grp->prm_f = 0: one pair), lay is a GroupedLayout's; the setup kernels run over the groups
+// The entry points below set a call up and run the path it was planned on; the 2-pass kernels' step sequences exist
+// once (two_pass_forward / two_pass_reverse on a TwoPass grid: a single or grouped solve, or the one-grid call's
+// branches), as do the isotropic norm step, the fused isotropic loops and the gradient assembly.
+// run_forward: np planes of the call from plane p0 on (default: all of them), through the layout `lay` at `ws`.  A
+// grouped call (c.grouped): h holds one PSF per group, sc.lam / sc.rho point at nparam device values, lay is
+// make_grouped_layout's (or a grouped BwdLayout's f); the setup kernels run over the groups.
 // tables = false: the workspace already holds this call's twiddles, C / G tables and scalar block (a later plane
 // chunk of the same call through the same chunk workspace): the setup kernels are not launched again
-int run_forward(Launcher& ln, const float* y, float* x_out, int M, int N, size_t planes, const float* h, int kh,
-                int kw, const admm::ScalarSrc& sc, int iso, int maxit, unsigned char* ws, const Layout& lay,
-                const Traj& tr, const admm_batch_reducer* red, int fwd_path, bool tables = true,
-                const admm::plane::Branches* grp = nullptr);
-// everything run_backward does after validating the call and updating the recordings registry
-int launch_backward(int phases, const float* y, const float* x_bar, float* y_bar, float* h_bar, float* lambda_bar,
-                    float* rho_bar, int M, int N, size_t planes, const float* h, int kh, int kw,
-                    const admm::ScalarSrc& sc, int iso, int maxit, float* x_out, void* workspace, void* stream,
-                    const admm_batch_reducer* red, const PathPlan& plan, const BwdLayout& bl);
+int run_forward(Launcher& ln, const Call& c, unsigned char* ws, const Layout& lay, const Traj& tr, int fwd_path,
+                bool tables = true, size_t p0 = 0, size_t np = 0);
+// everything run_backward does after validating the call and updating the recordings registry: phases & 1 the
+// recording forward, phases & 2 the reverse sweep and the assembly of the gradients; a single or a grouped call
+int launch_backward(int phases, const Call& c, const Grads& g, const PathPlan& plan, const BwdLayout& bl);
 int launch_forward_multi(const float* y, float* x_out, int M, int N, int P, int B, int nbr, const float* const* lambda,
                          const float* const* rho, int maxit, int flags, void* workspace, void* stream, size_t planes,
                          const MultiLayout& L);

@@ -88,3 +88,39 @@ MULTI_COUNTS = {
     (True, True): ((2, 2, 4, 6, 1, 3, 0, 0), (2, 3, 8, 6, 6, 6, 0, 7)),
     (True, False): ((4, 0, 0, 0, 0, 3, 4, 0), (4, 0, 0, 0, 5, 6, 4, 4)),
 }
+
+# the grouped adjoint (tests/test_gpu_grouped_adjoint.py grouped_launch_counts: K = 4, B = 2, P = 3, a group per plane,
+# 5 x 5 PSFs, the plane-count rule off): "MxN-prox-call-variant", call = record + replay counted together or the
+# combined call, variant = with h_bar ("h"), without ("noh"), or y_bar and rho_bar not asked for ("drop").
+# Recorded from commit 743899b, before the single and the grouped adjoint driver were merged into one
+# (admm_launch.hip launch_backward).
+GROUPED_COUNTS = {
+    "32x32-aniso-replay-h": (1, 3, 8, 3, 10, 0, 0, 4),
+    "32x32-aniso-replay-noh": (1, 3, 8, 3, 6, 0, 0, 4),
+    "32x32-aniso-replay-drop": (1, 3, 8, 3, 7, 0, 0, 4),
+    "32x32-aniso-combined-h": (1, 3, 8, 3, 10, 0, 0, 4),
+    "32x32-aniso-combined-noh": (1, 3, 8, 3, 6, 0, 0, 4),
+    "32x32-aniso-combined-drop": (1, 3, 8, 3, 7, 0, 0, 4),
+    "32x32-iso-replay-h": (1, 3, 8, 6, 10, 6, 0, 7),
+    "32x32-iso-replay-noh": (1, 3, 8, 6, 6, 6, 0, 7),
+    "32x32-iso-replay-drop": (1, 3, 8, 6, 7, 6, 0, 7),
+    "32x32-iso-combined-h": (1, 3, 8, 6, 10, 6, 0, 7),
+    "32x32-iso-combined-noh": (1, 3, 8, 6, 6, 6, 0, 7),
+    "32x32-iso-combined-drop": (1, 3, 8, 6, 7, 6, 0, 7),
+    "24x20-aniso-replay-h": (1, 3, 8, 10, 10, 0, 0, 4),
+    "24x20-aniso-replay-noh": (1, 3, 8, 10, 6, 0, 0, 4),
+    "24x20-aniso-replay-drop": (1, 3, 8, 10, 7, 0, 0, 4),
+    "24x20-aniso-combined-h": (1, 3, 8, 10, 10, 0, 0, 4),
+    "24x20-aniso-combined-noh": (1, 3, 8, 10, 6, 0, 0, 4),
+    "24x20-aniso-combined-drop": (1, 3, 8, 10, 7, 0, 0, 4),
+    "24x20-iso-replay-h": (1, 3, 8, 13, 10, 6, 0, 7),
+    "24x20-iso-replay-noh": (1, 3, 8, 13, 6, 6, 0, 7),
+    "24x20-iso-replay-drop": (1, 3, 8, 13, 7, 6, 0, 7),
+    "24x20-iso-combined-h": (1, 3, 8, 13, 10, 6, 0, 7),
+    "24x20-iso-combined-noh": (1, 3, 8, 13, 6, 6, 0, 7),
+    "24x20-iso-combined-drop": (1, 3, 8, 13, 7, 6, 0, 7),
+    "256x256-aniso-replay-noh": (2, 1, 4, 0, 5, 0, 1, 4),
+    "256x256-aniso-replay-drop": (2, 1, 4, 0, 2, 0, 1, 4),
+    "256x256-aniso-combined-noh": (2, 1, 4, 0, 5, 0, 1, 4),
+    "256x256-aniso-combined-drop": (2, 1, 4, 0, 2, 0, 1, 4),
+}

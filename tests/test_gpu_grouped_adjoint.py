@@ -7,7 +7,9 @@ admm_tvd_backward_grouped_*): gradients per PSF / (lambda, rho) group from one r
   b. anisotropic, every plane against its own single-PSF adjoint through the same kernels: x and y_bar bitwise, the
      scalars and h_bar (the same fp64 partial rows summed in another order, rounded to fp32 once) within 2 fp32 ulps;
   c. consistency (record + replay = the combined call, determinism, dropped outputs, G = 1, refusals);
-  d. autograd through tvd_fft_grouped_grad."""
+  d. autograd through tvd_fft_grouped_grad;
+  e. the launches per profiler class of the 2-pass, runtime-length and fused-trajectory sequences equal
+     tests/launch_counts.py GROUPED_COUNTS exactly."""
 import functools
 
 import numpy as np
@@ -17,6 +19,7 @@ import torch
 import admm_deconv
 from admm_deconv import _lib
 from grouped_oracle_torch import group_of, tvd_fft_grouped_grads
+from launch_counts import CLASSES, GROUPED_COUNTS
 from parity import assert_parity, assert_prox_active
 from test_gpu_backward import assert_grad, grad_errs, rel
 from test_gpu_grouped import make_case
@@ -279,6 +282,41 @@ def test_replay_with_another_gp_is_refused(dev):
     with pytest.raises(admm_deconv.AdmmError) as e:
         admm_deconv.tvd_fft_grouped_backward_recorded(rec, x, torch.ones_like(yd))
     assert e.value.code == _lib.ADMM_E_INVALID
+
+
+# ---- launches per profiler class (tests/launch_counts.py GROUPED_COUNTS) -------------------------------------------
+def grouped_launch_counts(dev, cid):
+    """The launches per class of one grouped adjoint call: K = 4, B = 2, P = 3, a group per plane, 5 x 5 PSFs; cid =
+    "MxN-prox-call-variant": call "replay" (record + replay, counted together) or "combined"; variant "h" (h_bar),
+    "noh" (need_h=False) or "drop" (need_y=False, need_rho=False).  Also checks the path the call was planned on."""
+    shape, prox, call, variant = cid.split("-")
+    M, N = (int(v) for v in shape.split("x"))
+    iso, B, P, K = prox == "iso", 2, 3, 4
+    need_h = variant != "noh" and M != 256   # 256 x 256: the fused lane-native trajectory (no h_bar)
+    kw = dict(need_y=variant != "drop", need_rho=variant != "drop")
+    y, hs, lams, rhos = make_case(B, P, N, M, B, P, ("rand", 5, 5), 0.0041, 0.021, K, iso, 1 if iso else B * P)
+    xbar = seeded_xbar(y.shape)
+    sfx = "_iso" if iso else ""
+    paths = {32: ("2pass" + sfx, "sweep_2pass" + sfx), 24: ("runtime", "sweep_runtime" + sfx), 256: ("fused", "sweep_2pass")}[M]
+    with _lib.option("MIN_PLANES", 0):
+        assert _lib.query_grouped_paths(M, N, iso, 5, B * P, B * P, flags=_lib.REC_HBAR if need_h else 0) == paths, cid
+        _lib.profile_reset()
+        _lib.profile_enable(True)
+        try:
+            if call == "replay":
+                run_recorded(dev, y, hs, B, P, lams, rhos, iso, K, xbar, need_h=need_h, **kw)
+            else:
+                run_combined(dev, y, hs, B, P, lams, rhos, iso, K, xbar, need_h=need_h, **kw)
+        finally:
+            _lib.profile_enable(False)
+    c = {name: _lib.profile_get(cls)[1] for cls, name in _lib.KERNEL_CLASSES.items()}
+    return tuple(c.get(name, 0) for name in CLASSES)
+
+
+@pytest.mark.parametrize("cid", sorted(GROUPED_COUNTS))
+def test_grouped_launch_counts(dev, cid):
+    got = grouped_launch_counts(dev, cid)
+    assert got == GROUPED_COUNTS[cid], f"{cid}: launches per class {dict(zip(CLASSES, got))}"
 
 
 # ---- d. autograd ----------------------------------------------------------------------------------------------------
