@@ -46,7 +46,8 @@ EXPORTS = ("admm_abi_version", "admm_last_error", "admm_tvd_workspace_bytes", "a
            "admm_tvd_grouped_workspace_bytes", "admm_tvd_forward_grouped_dev_f32", "admm_query_grouped_path",
            "admm_tvd_grouped_backward_workspace_bytes", "admm_tvd_forward_grouped_record_dev_f32",
            "admm_tvd_backward_grouped_recorded_dev_f32", "admm_tvd_backward_grouped_dev_f32",
-           "admm_query_grouped_paths")
+           "admm_query_grouped_paths",
+           "admm_tvd_state_workspace_bytes", "admm_tvd_forward_state_dev_f32", "admm_query_state_path")
 
 # record flags (the want_hbar word of the record entry points) and multi-branch flags
 REC_HBAR, REC_MASKS = 1, 2
@@ -195,6 +196,15 @@ def load():
     L.admm_tvd_backward_grouped_dev_f32.argtypes = list(L.admm_tvd_backward_grouped_recorded_dev_f32.argtypes)
     L.admm_query_grouped_paths.restype = c_int
     L.admm_query_grouped_paths.argtypes = [c_int] * 4 + [ctypes.c_longlong] + [c_int] * 5 + [ctypes.POINTER(c_int)] * 2
+    L.admm_tvd_state_workspace_bytes.restype = c_int
+    L.admm_tvd_state_workspace_bytes.argtypes = [c_int] * 7 + [ctypes.POINTER(c_size_t)]
+    # y, x_out, M, N, P, B, h, kh, kw, lambda, rho, iso, maxit, state_in, state_out, resid_out, workspace, bytes, stream
+    L.admm_tvd_forward_state_dev_f32.restype = c_int
+    L.admm_tvd_forward_state_dev_f32.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                                 c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p, c_size_t, c_void_p]
+    L.admm_query_state_path.restype = c_int
+    L.admm_query_state_path.argtypes = [c_int] * 4 + [ctypes.c_longlong, ctypes.POINTER(c_int)]
     L.admm_path_name.restype = ctypes.c_char_p
     L.admm_path_name.argtypes = [c_int]
     _lib = L
@@ -232,6 +242,20 @@ def grouped_workspace_bytes(M, N, P, B, gb, gp, kh, kw, iso):
     out = ctypes.c_size_t(0)
     check(load().admm_tvd_grouped_workspace_bytes(M, N, P, B, gb, gp, kh, kw, int(bool(iso)), ctypes.byref(out)))
     return out.value
+
+
+def state_workspace_bytes(M, N, P, B, kh, kw, iso):
+    out = ctypes.c_size_t(0)
+    check(load().admm_tvd_state_workspace_bytes(M, N, P, B, kh, kw, int(bool(iso)), ctypes.byref(out)))
+    return out.value
+
+
+def query_state_path(M, N, iso=False, kh=0, planes=0):
+    """admm_query_state_path: the forward path name of a state call (tvd_fft_state) of `planes` planes."""
+    L = load()
+    f = ctypes.c_int(0)
+    check(L.admm_query_state_path(M, N, int(bool(iso)), kh, int(planes), ctypes.byref(f)))
+    return L.admm_path_name(f.value).decode()
 
 
 def query_grouped_path(M, N, iso=False, kh=0, planes=0, groups=1):

@@ -22,7 +22,7 @@ from . import _lib
 __all__ = ["tvd_fft", "tvd_fft_backward", "tvd_fft_record", "tvd_fft_backward_recorded", "Recording", "Workspace",
            "tvd_fft_multi", "tvd_fft_multi_backward_recorded", "multi_supported", "tvd_fft_grouped",
            "tvd_fft_grouped_record", "tvd_fft_grouped_backward_recorded", "tvd_fft_grouped_backward", "tvd_fft_grouped_grad",
-           "GroupedRecording"]
+           "GroupedRecording", "tvd_fft_state", "tvd_fft_tol"]
 
 
 class Workspace:
@@ -434,6 +434,83 @@ def tvd_fft(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, out=None, wo
     if scalars is not None:
         lam, rho = scalars
     return _forward_raw(y, lam, rho, h, isotropic, maxit, out=out, workspace=workspace, stream=stream, group=group)
+
+
+# ---- resumable solve: ADMM state in and out, residual norms, stop on tolerance (inference) ----
+def tvd_fft_state(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, state=None, want_state=True,
+                  want_residuals=True, out=None, workspace=None, stream=None, _state_out=None):
+    """`maxit` >= 1 ADMM iterations from the state `state` (None: the zero state, i.e. tvd_fft) -- returns (x, state,
+    resid), each of the last two None where not wanted (admm_tvd_forward_state_dev_f32, include/admm_deconv.h).
+
+    state: float32 (B, P, 2, N, M), s_k = D x_k + u_{k-1} (channel 0 the difference along N, channel 1 along M): all an
+    ADMM solve carries over.  Feeding a call's state to the next continues the solve (a then b iterations = a + b);
+    the call's own lam / rho form the prox of the given state, so a warm start under other parameters is well defined.
+    resid: float32 (B, P, 4) = (|r|, |d|, pri, dual) per plane, the norms of the stopping rule (tvd_fft_tol).
+    Neither `y` nor `state` is modified.  Not differentiable: ValueError when an input requires grad under autograd."""
+    tensors = [t for t in (y, lam, rho, h, state) if isinstance(t, torch.Tensor)]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise ValueError("tvd_fft_state is not differentiable (use tvd_fft, or call it under torch.no_grad())")
+    if int(maxit) < 1:
+        raise ValueError("tvd_fft_state: maxit must be >= 1 (x is not part of the state)")
+    _, y4, hbuf = _prep(y, h, ranks=(4,))
+    B, P, N, M = y4.shape
+    kw, kh = (0, 0) if hbuf is None else hbuf.shape
+    if state is not None:
+        if (not isinstance(state, torch.Tensor) or state.shape != (B, P, 2, N, M) or state.dtype != torch.float32
+                or state.device != y.device):
+            raise ValueError(f"state must be a float32 tensor of shape {(B, P, 2, N, M)} on y's device")
+        state = state.detach().contiguous()
+    out = _out_like(out, y4)
+    stream, s_handle = _stream_of(stream, y.device)
+    workspace, ws_ptr, ws_len = _acquire("state", _lib.state_workspace_bytes(M, N, P, B, kh, kw, isotropic), y.device,
+                                         stream, workspace)
+    dv = _DevScalars(lam, rho, y.device, stream)
+    new = None
+    if want_state:   # (_state_out: tvd_fft_tol's ping-pong tensor, of this shape by construction)
+        new = _state_out if _state_out is not None else torch.empty((B, P, 2, N, M), dtype=torch.float32, device=y.device)
+    resid = torch.empty((B, P, 4), dtype=torch.float32, device=y.device) if want_residuals else None
+    _record_streams(stream, y.device, state, new, resid)
+    _lib.check(_lib.load().admm_tvd_forward_state_dev_f32(
+        y4.data_ptr(), out.data_ptr(), M, N, P, B, None if hbuf is None else hbuf.data_ptr(), kh, kw, *dv.ptrs,
+        int(bool(isotropic)), int(maxit), None if state is None else state.data_ptr(),
+        None if new is None else new.data_ptr(), None if resid is None else resid.data_ptr(), ws_ptr, ws_len, s_handle))
+    return out, new, resid
+
+
+def tvd_fft_tol(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, eps_abs=0.0, eps_rel=1e-3, check_every=10,
+                state=None, stream=None):
+    """tvd_fft that stops on convergence: blocks of `check_every` iterations (the last one shorter, so that iters <=
+    maxit) until every plane meets the standard ADMM stopping rule
+        |r| <= sqrt(2 M N) eps_abs + eps_rel pri   and   |d| <= sqrt(M N) eps_abs + eps_rel dual
+    (resid of tvd_fft_state).  Returns (x, state, iters, resid); iters is the total run.  The residuals are read back
+    once per block -- the call's only host synchronisation.  `state`: an optional warm start."""
+    maxit, check_every = int(maxit), int(check_every)
+    if maxit < 1 or check_every < 1:
+        raise ValueError("tvd_fft_tol: maxit and check_every must be >= 1")
+    _check_y(y, "tvd_fft_tol", (4,), "4-D (B, P, N, M)")
+    N, M = y.shape[-2:]
+    a_pri, a_dual = math.sqrt(2.0 * M * N) * eps_abs, math.sqrt(1.0 * M * N) * eps_abs
+    # lambda / rho once on the device: no per-block upload
+    stream_t, _ = _stream_of(stream, y.device)
+    dv = _DevScalars(lam, rho, y.device, stream_t)
+    x = resid = None
+    iters = 0
+    spare = None   # two state tensors take turns: a block reads one and writes the other (never the caller's)
+    while iters < maxit:
+        k = min(check_every, maxit - iters)
+        prev = state
+        x, state, resid = tvd_fft_state(y, dv.lam, dv.rho, h, isotropic, k, state=prev, out=x, stream=stream,
+                                        _state_out=spare)
+        spare = prev if iters > 0 else None
+        iters += k
+        # the block's only synchronisation: the residuals, read back behind the solve on its stream
+        with torch.cuda.stream(stream_t) if isinstance(stream_t, torch.cuda.Stream) else contextlib.nullcontext():
+            if not isinstance(stream_t, torch.cuda.Stream):
+                torch.cuda.synchronize(y.device)
+            r = resid.to("cpu", torch.float64)
+        if bool(((r[..., 0] <= a_pri + eps_rel * r[..., 2]) & (r[..., 1] <= a_dual + eps_rel * r[..., 3])).all()):
+            break
+    return x, state, iters, resid
 
 
 # ---- several ADMM branches of one shared input (Parallel(chcat, ...), src/nets/net_build.jl:113-125) ----

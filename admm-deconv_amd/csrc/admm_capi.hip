@@ -20,6 +20,7 @@
 #include <string>
 
 #include "capi_internal.hpp"
+#include "state_api.hpp"
 
 namespace admm {
 // admm_clamp_backward_f32: four elements per thread (16-B accesses when the three pointers allow), grid-strided
@@ -412,6 +413,50 @@ int forward_grouped(const Call& c) {
                      plan_grouped(c.M, c.N, c.iso != 0, c.planes()));
     const int rc2 = ln.finish();
     return rc ? rc : rc2;
+}
+
+// ---- resumable solve ----
+StateLayout make_state_layout(int M, int N, size_t planes, bool psf, bool iso) {
+    StateLayout L{};
+    L.f = make_layout(M, N, planes, psf, iso);
+    Carver cv{align_up(L.f.total)};
+    const size_t MN = (size_t)M * N;
+    L.v0 = cv.take(planes * MN * 4);
+    L.fmapK = iso ? cv.take(MN * 4) : 0;
+    L.rpart = cv.take(planes * (size_t)admm::st::resid_blocks(MN, planes) * admm::st::kResidSums * 8);
+    L.sK = fused_shape(M, N, iso) ? cv.take(planes * 2 * MN * 4) : 0;
+    L.total = cv.off;
+    return L;
+}
+
+int check_state_shape(int M, int N, int P, int B, int kh, int kw, int iso) {
+    const int rc = check_shape(M, N, P, B, kh, kw, iso);
+    if (rc) return rc;
+    if ((size_t)P * B > kChunkPlanes) return fail(ADMM_E_UNSUPPORTED, "state call: at most %zu planes per call", kChunkPlanes);
+    return ADMM_OK;
+}
+
+int forward_state(Call c, const float* state_in, float* state_out, float* resid_out) {
+    int rc = check_state_shape(c.M, c.N, c.P, c.B, c.kh, c.kw, c.iso);
+    if (rc) return rc;
+    if (c.kh > 0 && !c.h) return fail(ADMM_E_INVALID, "state call: h is NULL with a %d x %d PSF", c.kh, c.kw);
+    rc = check_common(c.y, c.x_out, c.maxit);
+    if (rc) return rc;
+    if (c.maxit < 1)
+        return fail(ADMM_E_INVALID, "state call: maxit must be >= 1 (x is not part of the state: no iteration, no x)");
+    if (state_out && state_out == state_in) return fail(ADMM_E_INVALID, "state call: state_out must not be state_in");
+    if ((reinterpret_cast<uintptr_t>(state_in) & 15) || (reinterpret_cast<uintptr_t>(state_out) & 15))
+        return fail(ADMM_E_INVALID, "state call: state_in and state_out must be 16-byte aligned");
+    const StateLayout L = make_state_layout(c.M, c.N, c.planes(), c.kh > 0, c.iso != 0);
+    rc = check_ws(c.workspace, c.workspace_bytes, L.total);
+    if (rc) return rc;
+    rec_forget(c.workspace);
+    unsigned char* ws = static_cast<unsigned char*>(c.workspace);
+    const StateIO st{state_in, state_out, resid_out, reinterpret_cast<float*>(ws + L.v0),
+                     c.iso ? reinterpret_cast<float*>(ws + L.fmapK) : nullptr, reinterpret_cast<double*>(ws + L.rpart),
+                     L.sK ? reinterpret_cast<float*>(ws + L.sK) : nullptr};
+    c.st = &st;
+    return launch_forward_state(c, L, plan_state(c.M, c.N, c.iso != 0, c.planes()));
 }
 
 BwdLayout make_grouped_bwd_layout(const Call& c, bool want_h) {
@@ -911,6 +956,27 @@ int admm_tvd_backward_grouped_dev_f32(const float* y, const float* x_bar, float*
     return run_backward(3, 0, ADMM_GROUPED(x_out), Grads{x_bar, y_bar, h_bar, lambda_bar, rho_bar});
 }
 #undef ADMM_GROUPED
+
+int admm_tvd_state_workspace_bytes(int M, int N, int P, int B, int kh, int kw, int iso, size_t* out_bytes) {
+    if (!out_bytes) return fail(ADMM_E_INVALID, "out_bytes is NULL");
+    const int rc = check_state_shape(M, N, P, B, kh, kw, iso);
+    if (rc) return rc;
+    // (the plain forward of the same arguments fits too: its MALL chunk schedule never needs more than the whole batch)
+    *out_bytes = std::max(make_state_layout(M, N, (size_t)P * B, kh > 0, iso != 0).total,
+                          forward_ws_bytes(M, N, (size_t)P * B, kh, iso != 0));
+    return ADMM_OK;
+}
+
+int admm_tvd_forward_state_dev_f32(const float* y, float* x_out, int M, int N, int P, int B, const float* h, int kh,
+                                   int kw, const float* lambda, const float* rho, int iso, int maxit,
+                                   const float* state_in, float* state_out, float* resid_out, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+    const int rc = check_dev_scalars(lambda, rho);
+    if (rc) return rc;
+    return forward_state(Call{y, x_out, M, N, P, B, h, kh, kw, dev_sc(lambda, rho), iso, maxit, workspace, workspace_bytes,
+                              stream, nullptr},
+                         state_in, state_out, resid_out);
+}
 
 int admm_tvd_multi_workspace_bytes(int M, int N, int P, int B, int nbranch, int maxit, int flags, size_t* out_bytes) {
     if (!out_bytes) return fail(ADMM_E_INVALID, "out_bytes is NULL");

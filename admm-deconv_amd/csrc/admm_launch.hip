@@ -14,6 +14,8 @@
 //   launch_backward      the one adjoint driver of single and grouped calls: recording forward, one reverse sweep (fused,
 //                        fused isotropic, runtime-length, 2-pass), assembly; grouping enters through Grouping only
 //   launch_*_multi       the one-grid multi-branch solve: the fused kernels, or the same TwoPass sequences
+//   launch_forward_state the resumable solve: the forward from s_0 (state_start: v_0 in place of the cleared first line
+//                        spectrum) or from the zero state, then the end kernels (s_K, residual norms; state_kernels.hip)
 // A call arrives as the Call / Grads descriptors of capi_internal.hpp, never as a positional parameter list.
 #include <hip/hip_runtime.h>
 
@@ -29,6 +31,7 @@
 #include "admm_generic_bwd.hip"
 #include "smooth_api.hpp"
 #include "resident_api.hpp"
+#include "state_api.hpp"
 
 namespace admm_capi {
 
@@ -343,6 +346,23 @@ int iso_norm_step(Launcher& ln, const float* part, float* fmap, int ngroups, siz
     });
 }
 
+// A state call's warm start: v_0 = rho D^T (z_0 - u_0) of the caller's s_0 into st.v0 -- isotropic: the batch norm of
+// s_0 first, its factor map left in fmap for iteration 1.  The caller line-transforms v_0 into the first line spectrum
+// (a cold call transforms zeros), and iteration 1 then reads s_0 as s_old with the kernels' s_zero / first flag off.
+int state_start(Launcher& ln, const StateIO& st, bool iso, int M, int N, size_t planes, float* part, float* fmap,
+                const float* prm) {
+    hipStream_t s = ln.s;
+    const size_t MN = (size_t)M * N;
+    if (iso) {
+        const int ng = iso_ngroups(planes);
+        int rc = ln.run(ADMM_K_NORM, [&] { return admm::st::launch_sq(st.in, part, MN, planes, iso_group(planes), ng, s); });
+        if (rc) return rc;
+        rc = iso_norm_step(ln, part, fmap, ng, MN, prm, nullptr, nullptr);
+        if (rc) return rc;
+    }
+    return ln.run(ADMM_K_PREP, [&] { return admm::st::launch_v0(st.in, iso ? fmap : nullptr, st.v0, M, N, planes, prm, s); });
+}
+
 // Iteration it = 1 .. K-1 reads s_{it-1} and writes s_it: a recording keeps s_it in trajectory slot it - 1; without
 // one the two buffers take turns (isotropic: b1 = b0, s is updated in place).  Iteration 1 reads no s (the kernels'
 // s_zero / first flag): so is then sn itself, any valid pointer would do.
@@ -461,8 +481,10 @@ int two_pass_conv(const TwoPass& c, int cls, int mode, const float* src, float* 
 // ISO_A over the plane groups, the batch norm, ISO_B) and the final inverse.
 // tr: s_it into trajectory slot it - 1, the dim-2 spectrum of iteration it (before the multiply, h_bar) into slot
 // it - 1 of tr.v, |s_it| into norm slot it - 1; b0 / b1: the s buffers without a recording (fwd_slots).
+// st (a state call) with st->in: the first line spectrum is that of v_0 (state_start) and iteration 1 reads s_0.
 int two_pass_forward(const TwoPass& c, const float* y, float* x_out, int maxit, bool iso, const Traj& tr, float* b0,
-                     float* b1, const admm_batch_reducer* red = nullptr) {
+                     float* b1, const admm_batch_reducer* red = nullptr, const StateIO* st = nullptr) {
+    const float* s0 = st ? st->in : nullptr;
     Launcher& ln = c.ln;
     hipStream_t s = ln.s;
     int rc = ln.run(ADMM_K_PREP, [&] {
@@ -474,8 +496,15 @@ int two_pass_forward(const TwoPass& c, const float* y, float* x_out, int maxit, 
                              c.G ? (float)c.MN : 1.0f, nullptr, nullptr, c.br, c.yh);
     });
     if (rc) return rc;
-    hipError_t e = hipMemsetAsync(c.spec0, 0, c.planes * c.MN * 4, s);
-    if (e != hipSuccess) return fail(ADMM_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    if (s0) {
+        rc = state_start(ln, *st, iso, c.M, c.N, c.planes, c.qpart, c.fmap, c.prm);
+        if (rc) return rc;
+        rc = ln.run(ADMM_K_PREP, [&] { return launch_line_fwd(c.L, c.T, c.gl, c.flds, s, st->v0, c.spec0, c.twM, c.N); });
+        if (rc) return rc;
+    } else {
+        hipError_t e = hipMemsetAsync(c.spec0, 0, c.planes * c.MN * 4, s);
+        if (e != hipSuccess) return fail(ADMM_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    }
     const size_t sstride = c.planes * 2 * c.MN;   // one trajectory slot of s
     for (int it = 1; it <= maxit; ++it) {
         float2* vsave = tr.v ? tr.v + (size_t)(it - 1) * c.planes * c.N * c.L : nullptr;
@@ -485,11 +514,13 @@ int two_pass_forward(const TwoPass& c, const float* y, float* x_out, int maxit, 
         });
         if (rc) return rc;
         if (it == maxit) break;
-        const Slots p = fwd_slots(it, tr.s, sstride, b0, b1);
+        Slots p = fwd_slots(it, tr.s, sstride, b0, b1);
+        const int sz = it == 1 && !s0 ? 1 : 0;
+        if (it == 1 && s0) p.so = s0;
         if (!iso) {
             rc = ln.run(ADMM_K_LINE, [&] {
                 return launch_line(c.L, c.Tu, c.gu, c.llds, s, c.spec1, c.spec0, p.so, p.sn, nullptr, c.twM, c.N, c.prm,
-                                   it == 1 ? 1 : 0, c.nTu, c.br);
+                                   sz, c.nTu, c.br);
             });
             if (rc) return rc;
             continue;
@@ -498,7 +529,7 @@ int two_pass_forward(const TwoPass& c, const float* y, float* x_out, int maxit, 
         // iteration writes its own slot and the batch norm is kept too
         rc = ln.run(ADMM_K_LINE, [&] {
             return launch_iso_a(c.L, c.T, dim3(c.N / c.T, (unsigned)c.ng), iso_a_lds(c.M, c.T), s, c.spec1, p.so, p.sn,
-                                c.fmap, c.qpart, c.twM, c.N, c.gplanes, c.Gp, it == 1 ? 1 : 0, c.ngb_k);
+                                c.fmap, c.qpart, c.twM, c.N, c.gplanes, c.Gp, sz, c.ngb_k);
         });
         if (rc) return rc;
         rc = iso_norm_step(ln, c.qpart, c.fmap, c.ngb, c.MN, c.prm, tr.nrm ? tr.nrm + (size_t)(it - 1) * c.nstride : nullptr,
@@ -651,6 +682,16 @@ int run_forward(Launcher& ln, const Call& c, unsigned char* ws, const Layout& la
             return pk::launch_tables(v.C, v.G, v.F, s);
         });
         if (rc) return rc;
+        if (c.st) {   // a state call: the kernel's state instance, from s_0 (v_0 first) or from the zero state
+            if (c.st->in) {
+                rc = state_start(ln, *c.st, false, M, N, planes, nullptr, nullptr, v.prm);
+                if (rc) return rc;
+            }
+            return ln.run(ADMM_K_PLANE, [&] {
+                return pk::launch_plane_state(y, x_out, v.F, kh > 0, v.spec0, reinterpret_cast<float4*>(v.s[0]), v.prm,
+                                              maxit, planes, s, c.st->in, c.st->in ? c.st->v0 : nullptr);
+            });
+        }
         // a grouped solve: the same descriptor over the lane-native table blocks
         Branches bf = br;
         bf.tab_f = (unsigned)(pk::grouped_tables_bytes() / 4);
@@ -690,7 +731,7 @@ int run_forward(Launcher& ln, const Call& c, unsigned char* ws, const Layout& la
                                     v.prm, maxit);
         });
     }
-    return two_pass_forward(t, y, x_out, maxit, iso != 0, tr, v.s[0], iso ? v.s[0] : v.s[1], red);
+    return two_pass_forward(t, y, x_out, maxit, iso != 0, tr, v.s[0], iso ? v.s[0] : v.s[1], red, c.st);
 }
 
 // ---- the runtime-length kernels (admm_generic.hip, admm_generic_bwd.hip) -----------------------------------
@@ -764,8 +805,9 @@ int run_forward_generic(Launcher& ln, const Call& c, const PlaneRange& r, const 
     const size_t planes = r.planes;
     const admm_batch_reducer* red = c.red;
     const size_t MN = (size_t)M * N;
-    // (a grouped solve runs the runtime-length kernels only: they take the group offsets)
-    const GenPass p = gen_pass(M, N, planes, opt(ADMM_OPT_SMOOTH) != 0 && br.nbr != 0);
+    // (a grouped solve runs the runtime-length kernels only: they take the group offsets; a state call too)
+    const GenPass p = gen_pass(M, N, planes, opt(ADMM_OPT_SMOOTH) != 0 && br.nbr != 0 && !c.st);
+    const float* s0 = c.st ? c.st->in : nullptr;
     set_lds(g::line_upd_kernel, p.lup);
     set_lds(g::iso_b_kernel, p.lup);
     const size_t sstride = planes * 2 * MN;   // one trajectory slot of s
@@ -794,8 +836,15 @@ int run_forward_generic(Launcher& ln, const Call& c, const PlaneRange& r, const 
         return 0;
     });
     if (rc) return rc;
-    hipError_t e = hipMemsetAsync(v.spec0, 0, planes * (size_t)p.H * N * 8, s);   // iteration 1: w = 0
-    if (e != hipSuccess) return fail(ADMM_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    if (s0) {   // a warm state call: the line spectrum of v_0 = rho D^T (z_0 - u_0)
+        rc = state_start(ln, *c.st, iso != 0, M, N, planes, v.part, v.fmap, v.prm);
+        if (rc) return rc;
+        rc = gen_line_fwd(ln, p, v, ADMM_K_PREP, c.st->v0, v.spec0);
+        if (rc) return rc;
+    } else {
+        hipError_t e = hipMemsetAsync(v.spec0, 0, planes * (size_t)p.H * N * 8, s);   // iteration 1: w = 0
+        if (e != hipSuccess) return fail(ADMM_E_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    }
     const int ng = iso_ngroups(planes);
     for (int it = 1; it <= maxit; ++it) {
         // trajectory for h_bar: the dim-2 spectrum of iteration it before the multiply
@@ -813,14 +862,16 @@ int run_forward_generic(Launcher& ln, const Call& c, const PlaneRange& r, const 
         rc = gen_line_inv(ln, p, v, last ? ADMM_K_FINAL : ADMM_K_LINE, v.spec1, last ? x_out : v.xg);
         if (rc) return rc;
         if (last) break;
-        const Slots sl = fwd_slots(it, tr.s, sstride, v.s[0], iso ? v.s[0] : v.s[1]);
+        Slots sl = fwd_slots(it, tr.s, sstride, v.s[0], iso ? v.s[0] : v.s[1]);
+        const int first = it == 1 && !s0 ? 1 : 0;
+        if (it == 1 && s0) sl.so = s0;
         if (!iso) {
             rc = ln.run(ADMM_K_LINE, [&] {
                 if (p.sml)
                     return admm::sm::launch_line_upd(M, N, planes, s, v.xg, sl.so, sl.sn, nullptr, v.spec0, v.twM, v.prm,
-                                                     it == 1 ? 1 : 0);
+                                                     first);
                 hipLaunchKernelGGL(g::line_upd_kernel, p.gl, dim3(256), p.lup, s, v.xg, sl.so, sl.sn, (const float*)nullptr,
-                                   v.spec0, v.twM, p.pM, N, p.T, v.prm, it == 1 ? 1 : 0, br);
+                                   v.spec0, v.twM, p.pM, N, p.T, v.prm, first, br);
                 return 0;
             });
             if (rc) return rc;
@@ -828,7 +879,7 @@ int run_forward_generic(Launcher& ln, const Call& c, const PlaneRange& r, const 
         }
         rc = ln.run(ADMM_K_LINE, [&] {
             hipLaunchKernelGGL(g::iso_a_kernel, dim3(gen_nb(N, p.T), ng), dim3(256), (size_t)p.T * M * 4, s, v.xg, sl.so,
-                               sl.sn, v.fmap, v.part, M, N, (int)planes, iso_group(planes), p.T, it == 1 ? 1 : 0);
+                               sl.sn, v.fmap, v.part, M, N, (int)planes, iso_group(planes), p.T, first);
         });
         if (rc) return rc;
         rc = iso_norm_step(ln, v.part, v.fmap, ng, MN, v.prm, tr.nrm ? tr.nrm + (size_t)(it - 1) * MN : nullptr, red);
@@ -1484,6 +1535,55 @@ int launch_line_adj_grouped(int L, int T, dim3 g, size_t lds, hipStream_t s, con
     XG(128, 2, true) XG(128, 4, true) XG(128, 8, true) XG(128, 16, true)
 #undef XG
     return -1;
+}
+
+// ---- resumable solve --------------------------------------------------------------------------------------------
+// The forward on the planned path (fused, 2-pass or runtime-length, from s_0 or the zero state), then the end kernels.
+// 2-pass and runtime-length: after K iterations the s buffers hold s_{K-1} (K = 1: the caller's s_0, or nothing) and, isotropic, fmap its factor map;
+// s_K = D x_K + u_{K-1} goes to state_out -- or, wanted for the residuals only, to the s buffer that is free.  The
+// residual norms need z_K: isotropic, one more norm step over s_K (its factor map in st.fmapK).
+int launch_forward_state(const Call& c, const StateLayout& L, int path) {
+    Launcher ln{reinterpret_cast<hipStream_t>(c.stream), g_prof.on, {}};
+    hipStream_t s = ln.s;
+    unsigned char* ws = static_cast<unsigned char*>(c.workspace);
+    const StateIO& st = *c.st;
+    const bool iso = c.iso != 0;
+    const int M = c.M, N = c.N, K = c.maxit;
+    const size_t planes = c.planes(), MN = (size_t)M * N;
+    int rc = run_forward(ln, c, ws, L.f, Traj{}, path);
+    const FwdView v = view(ws, L.f, c.kh > 0);
+    if (!rc && (st.out || st.resid) && path == ADMM_PATH_FUSED) {
+        // the fused kernel left s_{K-1} lane-native in s buffer 0 (K = 1: the imported s_0, or nothing); the residual
+        // pass reads it in the natural layout from s buffer 1
+        const float4* sln = K == 1 && !st.in ? nullptr : reinterpret_cast<const float4*>(v.s[0]);
+        float* sK = st.out ? st.out : st.sK;
+        float* s_prev = st.resid && sln ? v.s[1] : nullptr;
+        rc = ln.run(ADMM_K_FINAL, [&] {
+            return admm::plane::launch_state_end_lane(c.x_out, sln, sK, s_prev, v.prm, planes, s);
+        });
+        if (!rc && st.resid) rc = ln.run(ADMM_K_FINAL, [&] {
+            return admm::st::launch_resid(sK, s_prev, nullptr, nullptr, false, st.rpart, st.resid, M, N, planes, v.prm, s);
+        });
+    } else if (!rc && (st.out || st.resid)) {
+        // fwd_slots: iteration K - 1 wrote s_{K-1} to buffer 0 when K - 1 is odd or the prox isotropic (in place)
+        const float* s_prev = K == 1 ? st.in : (iso || ((K - 1) & 1)) ? v.s[0] : v.s[1];
+        float* sK = st.out ? st.out : s_prev == v.s[0] ? v.s[1] : v.s[0];
+        rc = ln.run(ADMM_K_FINAL, [&] {
+            return admm::st::launch_end(c.x_out, s_prev, v.fmap, iso, sK, M, N, planes, v.prm, s);
+        });
+        if (!rc && st.resid) {
+            if (iso) {
+                const int ng = iso_ngroups(planes);
+                rc = ln.run(ADMM_K_NORM, [&] { return admm::st::launch_sq(sK, v.part, MN, planes, iso_group(planes), ng, s); });
+                if (!rc) rc = iso_norm_step(ln, v.part, st.fmapK, ng, MN, v.prm, nullptr, nullptr);
+            }
+            if (!rc) rc = ln.run(ADMM_K_FINAL, [&] {
+                return admm::st::launch_resid(sK, s_prev, st.fmapK, v.fmap, iso, st.rpart, st.resid, M, N, planes, v.prm, s);
+            });
+        }
+    }
+    const int rc2 = ln.finish();
+    return rc ? rc : rc2;
 }
 
 }  // namespace admm_capi

@@ -232,6 +232,17 @@ PathPlan plan_grouped_adjoint(int M, int N, bool iso, bool psf, size_t planes, b
     return pl;
 }
 
+// Resumable solve (state in and out, residual norms): the kernels that can start from a given s_0.  256 x 256
+// anisotropic from the fused kernel's plane count on: plane256_kernel's state instance (plane_state.hip); the other
+// tuned shapes (and 256 x 256 below the rule, or isotropic): the 2-pass kernels; every other shape: the runtime-length
+// kernels.  The smooth-length, CU-resident and fused isotropic kernels have no state form.
+int plan_state(int M, int N, bool iso, size_t planes) {
+    if (generic_shape(M, N)) return ADMM_PATH_RUNTIME;
+    const PathIn q{M, N, iso, true, ADMM_MODE_FORWARD, 0, false, false, planes};
+    if (fused_shape(M, N, iso) && fused_enabled() && enough_planes(q, kMinFused)) return ADMM_PATH_FUSED;
+    return iso ? ADMM_PATH_2PASS_ISO : ADMM_PATH_2PASS;
+}
+
 // lines per block: the largest of 8, 4, 2, 1 dividing N with T * M <= 4096 (LDS ~ 24 T M bytes)
 // options ADMM_OPT_GEN_TM (max T x M of a line block), ADMM_OPT_GEN_KN (max KB x N of a column block)
 int gen_opt(int k, int dflt) {
@@ -338,6 +349,16 @@ int admm_query_grouped_paths(int M, int N, int iso, int kh, long long planes, in
     const PathPlan pl = plan_grouped_adjoint(M, N, iso != 0, kh > 0, (size_t)planes, want_h);
     *fwd_path = pl.fwd;
     *bwd_path = pl.bwd;
+    return ADMM_OK;
+}
+
+int admm_query_state_path(int M, int N, int iso, int kh, long long planes, int* fwd_path) {
+    if (!fwd_path) return fail(ADMM_E_INVALID, "admm_query_state_path: NULL output");
+    const int rc = check_shape(M, N, 1, 1, kh, kh > 0 ? 1 : 0, iso);   // (kw is not given: any kw <= N)
+    if (rc) return rc;
+    if (planes < 0 || planes > (long long)kChunkPlanes)
+        return fail(ADMM_E_INVALID, "admm_query_state_path: planes must be 0 .. %zu", kChunkPlanes);
+    *fwd_path = plan_state(M, N, iso != 0, (size_t)planes);
     return ADMM_OK;
 }
 

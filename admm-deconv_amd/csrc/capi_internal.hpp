@@ -224,6 +224,20 @@ size_t multi_F_bytes();
 size_t multi_iso_rows(int K);
 admm::plane::Branches multi_branches(int P, int B, int nbr);
 
+// ---- resumable solve (admm_tvd_forward_state_dev_f32) ----
+// What a state call reads and writes besides y and x_out (null: not given / not wanted), and its own workspace slots
+// behind the forward layout: the start kernel's v_0 plane set, the batch factor map of s_K (isotropic residuals) and
+// the residual pass's block sums.
+struct StateIO {
+    const float* in;   // s_0, natural layout (planes x 2 x N x M)
+    float* out;        // s_K
+    float* resid;      // planes x 4
+    float* v0;
+    float* fmapK;
+    double* rpart;
+    float* sK;         // the fused path's s_K when state_out is not wanted (residuals only), natural layout
+};
+
 // ---- the call descriptor ----
 // What a solve is.  Every extern "C" entry point of the single and the grouped family fills one in once, and
 // everything below the ABI receives it by const reference.
@@ -241,6 +255,7 @@ struct Call {
     const admm_batch_reducer* red;   // the batch reducer, only where it acts: isotropic and fn set
     int gb = 1, gp = 1, nparam = 1;  // the grouping (admm_tvd_*_grouped_*); a single solve: one group, one pair
     bool grouped = false;
+    const StateIO* st = nullptr;     // a state call: never the smooth-length kernels, warm start when st->in is set
     size_t planes() const { return (size_t)P * B; }
     int groups() const { return gb * gp; }
 };
@@ -290,6 +305,20 @@ inline int group_split(long long n) {
     return p < 1 ? 1 : p > 256 ? 256 : (int)p;
 }
 
+// ---- resumable solve: path and workspace ----
+// One path decision (admm_paths.hip), reported by admm_query_state_path: the fused kernel's state instance at 256 x 256
+// anisotropic from the fused kernel's plane count, the 2-pass kernels at the other tuned power-of-two shapes (and at
+// 256 x 256 isotropic or below the plane-count rule), the runtime-length kernels elsewhere, both proxes.  Never the
+// smooth-length, CU-resident or fused isotropic kernels, never the MALL chunk schedule: those take no s_0.
+int plan_state(int M, int N, bool iso, size_t planes);
+// Workspace: the forward layout of the whole batch, then v_0, the factor map of s_K (isotropic), the residual block
+// sums and (256 x 256 anisotropic) a natural-layout s_K for a fused call that wants residuals without state_out.
+struct StateLayout {
+    Layout f;
+    size_t v0, fmapK, rpart, sK, total;
+};
+StateLayout make_state_layout(int M, int N, size_t planes, bool psf, bool iso);
+
 // ---- launch sequencing (admm_launch.hip) ----
 // The entry points below set a call up and run the path it was planned on; the 2-pass kernels' step sequences exist
 // once (two_pass_forward / two_pass_reverse on a TwoPass grid: a single or grouped solve, or the one-grid call's
@@ -304,6 +333,8 @@ int run_forward(Launcher& ln, const Call& c, unsigned char* ws, const Layout& la
 // everything run_backward does after validating the call and updating the recordings registry: phases & 1 the
 // recording forward, phases & 2 the reverse sweep and the assembly of the gradients; a single or a grouped call
 int launch_backward(int phases, const Call& c, const Grads& g, const PathPlan& plan, const BwdLayout& bl);
+// a state call (c.st set): the forward on `path` from s_0 or the zero state, then the end kernels (s_K, residual norms)
+int launch_forward_state(const Call& c, const StateLayout& L, int path);
 int launch_forward_multi(const float* y, float* x_out, int M, int N, int P, int B, int nbr, const float* const* lambda,
                          const float* const* rho, int maxit, int flags, void* workspace, void* stream, size_t planes,
                          const MultiLayout& L);

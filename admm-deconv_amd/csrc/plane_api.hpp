@@ -99,6 +99,18 @@ hipError_t launch_plane_grouped_rec(const float* y, float* x_out, const void* ta
                                     const float* prm, int K, size_t planes, hipStream_t s, float4* traj,
                                     const Branches& br);
 
+// The resumable solve at 256 x 256 anisotropic (plane_state.hip, the kernel's TRAJ = 3 instantiations): all K >= 1
+// iterations from the zero state, or (state_in and v0 both given) from s_0 = state_in -- natural layout, planes x 2 x 256
+// x 256, imported into sln first -- with v0 = rho D^T (z_0 - u_0) (natural layout) added to H^T y.  sln holds s_{K-1}
+// lane-native afterwards (K = 1: s_0, or nothing from the zero state).
+hipError_t launch_plane_state(const float* y, float* x_out, const void* tables, bool psf, float2* hln, float4* sln,
+                              const float* prm, int K, size_t planes, hipStream_t s, const float* state_in,
+                              const float* v0);
+// s_out = s_K = D x_K + clip(s_{K-1}) in the natural layout, from x_K and the lane-native s_{K-1} (sln NULL: zero);
+// s_prev (or NULL) receives s_{K-1} in the natural layout.
+hipError_t launch_state_end_lane(const float* x, const float4* sln, float* s_out, float* s_prev, const float* prm,
+                                 size_t planes, hipStream_t s);
+
 // Reverse sweep of the anisotropic solve on the fused trajectory (plane256_adj_kernel):
 // launch_dx_lane writes D x_K (x_K = the forward output, natural layout) in the lane-native s layout;
 // launch_plane_adj runs steps K..1 for every plane.  traj: the forward's s_1..s_{K-1}; sbar, vsl: planes x

@@ -530,6 +530,11 @@ __device__ __forceinline__ void dbg_dump(float2* dbg, const float2 (&S)[64], int
 // k-2, instead of updating sln in place.  Same bytes per iteration as the plain solve.
 // TRAJ 2: record the ST mask bits of s_k instead (mask_byte): s stays in place in sln as in the plain solve,
 // and iteration k writes its mask slot k-1 (mtraj + (k-1) * mslot dwords, plane p at p * 16 * 512).
+// TRAJ 3: the state instance of the resumable solve (plane_state.hip).  s stays in place in sln and s_{K-1} is stored
+// (the store resource stays live for every k <= K - 1, as in TRAJ 1): the end kernel forms s_K from it.  mtraj, when set,
+// is not a mask trajectory but v_0 = rho D^T (z_0 - u_0) of a warm start (floats, natural layout, a plane 65536 apart):
+// it joins H^T y before the first line transform, sln then holds s_0 (state_import_kernel) and iteration 1 reads it
+// with the full-size resource and first = false.  mtraj NULL: the cold start, zero-size resource at k = 1 as above.
 // br: several branches in one grid (Branches; nbr = 1 is a single solve).
 // GRP: a grouped solve (br.nbr = 0): plane q reads and writes plane q with the tables and scalars of group_of(q).
 template <bool PSF, int DBG = 0, int TRAJ = 0, bool GRP = false>
@@ -590,6 +595,18 @@ __global__ __launch_bounds__(kPT) void plane256_kernel(const float* __restrict__
     }
 #pragma unroll
     for (int n = 0; n < 64; ++n) bst2(hp, t * 8, n * kPT * 8, S[n]);
+    if constexpr (TRAJ == 3) {
+        if (mtraj) {   // warm start: v = H^T y + v_0, a natural-layout row read like yrow
+            const float2* vrow = reinterpret_cast<const float2*>(reinterpret_cast<const float*>(mtraj) +
+                                                                 plane * 65536 + (size_t)r * 256);
+#pragma unroll
+            for (int n = 0; n < 64; ++n) {
+                const float2 a = vrow[2 * n + hb];
+                S[n].x += a.x;
+                S[n].y += a.y;
+            }
+        }
+    }
     line_forward_pair(S, hb);
     dbg_dump<DBG>(dbg, S, 0, t);
     for (int k = 1;; ++k) {
@@ -627,6 +644,10 @@ __global__ __launch_bounds__(kPT) void plane256_kernel(const float* __restrict__
             const rsrc_t sst = k <= K - 2 ? sp : make_rsrc(sln, 0);
             const rsrc_t mrs = make_rsrc(mtraj + (size_t)(k - 1) * mslot + plane * 16 * kPT, kMaskSlotBytes);
             row_update<kStage, true>(S, sld, sst, hp, xb, wb, sink, colbuf, t, hb, k == 1, tau, rho, mrs);
+        } else if constexpr (TRAJ == 3) {
+            const bool warm = mtraj != nullptr;
+            const rsrc_t sld = (k >= 2 || warm) ? sp : make_rsrc(sln, 0);
+            row_update<kStage>(S, sld, sp, hp, xb, wb, sink, colbuf, t, hb, k == 1 && !warm, tau, rho, sld);
         } else {
             // ... and s_{K-1} is never read (iteration K stops at x): its stores drop the same way
             const rsrc_t sld = k >= 2 ? sp : make_rsrc(sln, 0);

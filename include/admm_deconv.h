@@ -386,6 +386,53 @@ const char* admm_path_name(int path);
 int admm_query_forward_schedule(int M, int N, int iso, int kh, long long planes, long long* chunk_planes,
                                 int* streams);
 
+/* Resumable solve: ADMM state in and out, residual norms (inference: continue a solve, warm-start the next frame or
+ * tile, stop on convergence; the reference's loop always starts from zero, ops.jl:46-49, and carries objfun_iso /
+ * objfun_aniso, ops.jl:13-14, without using them).
+ *
+ * The state.  The whole per-pixel ADMM state after k iterations is one tensor s_k = D x_k + u_{k-1}: z_k = prox(s_k,
+ * lambda / rho) and u_k = s_k - z_k follow from it, and neither x nor a spectrum carries over between iterations.
+ * state_in / state_out are `float[B][P][2][N][M]`.  In terms of oracle_np.D_op (ops.jl:52-54), which maps the (M,N,B,P)
+ * working array to 2B channels, plane (b, p) holds
+ *     state[b][p][0][j][i] = x[j][i] - x[j-1][i]   D_op's output channel 2b   (0-based; the difference along dim 2, N)
+ *     state[b][p][1][j][i] = x[j][i] - x[j][i-1]   D_op's output channel 2b+1 (the difference along dim 1, M)
+ * plus u_{k-1} in the same positions, periodic.  This assignment is public contract.
+ *  - state_out receives s_K = D x_K + u_{K-1}.  NULL: not wanted.
+ *  - state_in = s_0 starts the call from z_0 = prox(s_0, lambda / rho), u_0 = s_0 - z_0, the prox being ST, or BT over
+ *    the whole batch when iso is set.  NULL: the zero state, the reference's init.  The call's own lambda and rho form
+ *    the prox of s_0, so warm-starting under a changed lambda or rho is well defined.
+ *  - Composition: a call with maxit = a followed by a call with maxit = b and state_in = the first call's state_out is
+ *    the a + b iteration solve (in exact arithmetic; same y, h, lambda, rho and prox).
+ *  - resid_out: `float[B*P][4]` = {|r|, |d|, pri, dual} per plane, 2-norms over the plane's pixels (r over both
+ *    channels):  r = D x_K - z_K (= u_K - u_{K-1}),  d = rho D^T (z_K - z_{K-1}),  pri = max(|D x_K|, |z_K|),
+ *    dual = rho |D^T u_K| -- the quantities of the standard stopping rule
+ *        |r| <= sqrt(2 M N) eps_abs + eps_rel pri   and   |d| <= sqrt(M N) eps_abs + eps_rel dual.
+ *    fp64 sums in a fixed order, no atomics.  With iso set, z_K = BT(s_K) takes one more batch norm, of s_K.
+ *    NULL: not wanted.
+ * Rules: lambda, rho device scalars as in the other _dev entry points; maxit >= 1 (maxit = 0 is ADMM_E_INVALID: x is
+ * not part of the state, so without an iteration there is no x to return); state_out must not be state_in
+ * (ADMM_E_INVALID; the dual residual reads neighbours of both) nor overlap it; h == NULL needs kh == kw == 0; at most
+ * 65,280 planes per call, not chunked.  No sharded, grouped or multi-branch form, no adjoint.  Asynchronous on `stream`,
+ * allocates nothing, deterministic, never modifies y or state_in.  Workspace: admm_tvd_state_workspace_bytes (the
+ * forward layout, one v_0 plane set, the residual partial sums, at 256 x 256 anisotropic one more state plane set;
+ * never less than admm_tvd_workspace_bytes).
+ * Paths (admm_query_state_path; the library options apply): ADMM_PATH_FUSED at 256 x 256 anisotropic from the fused
+ * kernel's plane count (ADMM_OPT_MIN_PLANES; its state instance keeps s lane-native, an import and an end kernel
+ * translate), ADMM_PATH_2PASS / ADMM_PATH_2PASS_ISO at the other tuned power-of-two shapes and at 256 x 256 when
+ * isotropic, below the plane-count rule or with ADMM_OPT_FUSED = 0, ADMM_PATH_RUNTIME for every other shape, both
+ * proxes.  State calls never take the smooth-length, CU-resident or fused isotropic kernels, nor the MALL chunk
+ * schedule: the shapes those serve run the runtime-length or 2-pass kernels instead.
+ * With state_in, state_out and resid_out all NULL, x_out is bitwise admm_tvd_forward_dev_f32's through the same path. */
+int admm_tvd_state_workspace_bytes(int M, int N, int P, int B, int kh, int kw, int iso, size_t* out_bytes);
+int admm_tvd_forward_state_dev_f32(const float* y, float* x_out, int M, int N, int P, int B,
+                                   const float* h, int kh, int kw, const float* lambda, const float* rho,
+                                   int iso, int maxit,
+                                   const float* state_in,   /* NULL: zero state (the reference's init) */
+                                   float* state_out,        /* NULL: not wanted */
+                                   float* resid_out,        /* NULL: not wanted; float[B*P][4] */
+                                   void* workspace, size_t workspace_bytes, void* stream);
+int admm_query_state_path(int M, int N, int iso, int kh, long long planes, int* fwd_path);
+
 /* The gradient of the layers' clamp activations (sigma = relu1 = min.(relu.(x), 1), src/nets/net_build.jl:8, and
  * relu6): dx[i] = (lo <= x[i] <= hi) ? dy[i] : 0 over n floats in one pass (autograd's form of the clamp is three
  * kernels).  x, dy, dx device pointers (dx may be dy); ADMM_E_INVALID for NULL pointers when n > 0. */
