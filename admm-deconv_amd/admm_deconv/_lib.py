@@ -47,11 +47,32 @@ EXPORTS = ("admm_abi_version", "admm_last_error", "admm_tvd_workspace_bytes", "a
            "admm_tvd_grouped_backward_workspace_bytes", "admm_tvd_forward_grouped_record_dev_f32",
            "admm_tvd_backward_grouped_recorded_dev_f32", "admm_tvd_backward_grouped_dev_f32",
            "admm_query_grouped_paths",
-           "admm_tvd_state_workspace_bytes", "admm_tvd_forward_state_dev_f32", "admm_query_state_path")
+           "admm_tvd_state_workspace_bytes", "admm_tvd_forward_state_dev_f32", "admm_query_state_path",
+           "admm_iso_plane_supported")
 
 # record flags (the want_hbar word of the record entry points) and multi-branch flags
 REC_HBAR, REC_MASKS = 1, 2
 MULTI_RECORD, MULTI_ISO = 1, 4
+
+# the prox (the `iso` argument of the C ABI, ADMM_ISO_*)
+ISO_NONE, ISO_BATCH, ISO_PLANE = 0, 1, 2
+
+
+def iso_code(isotropic):
+    """The C ABI's `iso` of an `isotropic` argument: False / True as ever (0: anisotropic, 1: the reference's
+    batch-coupled block-thresholding), "plane": isotropic TV of every image plane on its own (2).  Any other string is
+    an error -- a truthy string would otherwise silently select the batch-coupled prox."""
+    if isinstance(isotropic, str):
+        if isotropic == "plane":
+            return ISO_PLANE
+        raise ValueError(f'isotropic must be False, True or "plane" (got {isotropic!r})')
+    return int(bool(isotropic))
+
+
+def no_plane_mode(isotropic, who):
+    """ValueError from the entry points without a per-plane isotropic form."""
+    if iso_code(isotropic) == ISO_PLANE:
+        raise ValueError(f'{who}: isotropic="plane" is not supported here (False or True only)')
 
 
 # admm_reduce_fn / admm_batch_reducer (include/admm_deconv.h): cross-shard sum of an M x N map
@@ -87,6 +108,8 @@ def load():
     c_int, c_float, c_size_t, c_void_p = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
     L.admm_abi_version.restype = c_int
     L.admm_abi_version.argtypes = []
+    L.admm_iso_plane_supported.restype = c_int
+    L.admm_iso_plane_supported.argtypes = []
     L.admm_last_error.restype = ctypes.c_char_p
     L.admm_last_error.argtypes = []
     L.admm_tvd_workspace_bytes.restype = c_int
@@ -219,7 +242,7 @@ def check(rc):
 
 def workspace_bytes(M, N, P, B, kh, kw, iso):
     out = ctypes.c_size_t(0)
-    check(load().admm_tvd_workspace_bytes(M, N, P, B, kh, kw, int(bool(iso)), ctypes.byref(out)))
+    check(load().admm_tvd_workspace_bytes(M, N, P, B, kh, kw, iso_code(iso), ctypes.byref(out)))
     return out.value
 
 
@@ -227,7 +250,7 @@ def backward_workspace_bytes(M, N, P, B, kh, kw, iso, maxit, want_hbar):
     """want_hbar: a bool (h_bar wanted) or the flag word REC_HBAR | REC_MASKS."""
     out = ctypes.c_size_t(0)
     flags = int(want_hbar)
-    check(load().admm_tvd_backward_workspace_bytes(M, N, P, B, kh, kw, int(bool(iso)), int(maxit), flags,
+    check(load().admm_tvd_backward_workspace_bytes(M, N, P, B, kh, kw, iso_code(iso), int(maxit), flags,
                                                    ctypes.byref(out)))
     return out.value
 
@@ -240,13 +263,13 @@ def multi_workspace_bytes(M, N, P, B, nbranch, maxit, flags):
 
 def grouped_workspace_bytes(M, N, P, B, gb, gp, kh, kw, iso):
     out = ctypes.c_size_t(0)
-    check(load().admm_tvd_grouped_workspace_bytes(M, N, P, B, gb, gp, kh, kw, int(bool(iso)), ctypes.byref(out)))
+    check(load().admm_tvd_grouped_workspace_bytes(M, N, P, B, gb, gp, kh, kw, iso_code(iso), ctypes.byref(out)))
     return out.value
 
 
 def state_workspace_bytes(M, N, P, B, kh, kw, iso):
     out = ctypes.c_size_t(0)
-    check(load().admm_tvd_state_workspace_bytes(M, N, P, B, kh, kw, int(bool(iso)), ctypes.byref(out)))
+    check(load().admm_tvd_state_workspace_bytes(M, N, P, B, kh, kw, iso_code(iso), ctypes.byref(out)))
     return out.value
 
 
@@ -254,7 +277,7 @@ def query_state_path(M, N, iso=False, kh=0, planes=0):
     """admm_query_state_path: the forward path name of a state call (tvd_fft_state) of `planes` planes."""
     L = load()
     f = ctypes.c_int(0)
-    check(L.admm_query_state_path(M, N, int(bool(iso)), kh, int(planes), ctypes.byref(f)))
+    check(L.admm_query_state_path(M, N, iso_code(iso), kh, int(planes), ctypes.byref(f)))
     return L.admm_path_name(f.value).decode()
 
 
@@ -262,7 +285,7 @@ def query_grouped_path(M, N, iso=False, kh=0, planes=0, groups=1):
     """admm_query_grouped_path: the forward path name of a grouped call of `planes` planes in `groups` groups."""
     L = load()
     f = ctypes.c_int(0)
-    check(L.admm_query_grouped_path(M, N, int(bool(iso)), kh, int(planes), int(groups), ctypes.byref(f)))
+    check(L.admm_query_grouped_path(M, N, iso_code(iso), kh, int(planes), int(groups), ctypes.byref(f)))
     return L.admm_path_name(f.value).decode()
 
 
@@ -272,7 +295,7 @@ MODE_FORWARD, MODE_RECORD, MODE_BACKWARD = 0, 1, 2
 def grouped_backward_workspace_bytes(M, N, P, B, gb, gp, kh, kw, iso, maxit, rec_flags=0):
     """rec_flags: REC_HBAR when h_bar will be wanted (REC_MASKS is accepted and not honoured)."""
     out = ctypes.c_size_t(0)
-    check(load().admm_tvd_grouped_backward_workspace_bytes(M, N, P, B, gb, gp, kh, kw, int(bool(iso)), int(maxit),
+    check(load().admm_tvd_grouped_backward_workspace_bytes(M, N, P, B, gb, gp, kh, kw, iso_code(iso), int(maxit),
                                                            int(rec_flags), ctypes.byref(out)))
     return out.value
 
@@ -282,7 +305,7 @@ def query_grouped_paths(M, N, iso=False, kh=0, planes=0, groups=1, mode=MODE_REC
     """admm_query_grouped_paths: (forward path name, reverse-sweep path name or None) of a grouped call."""
     L = load()
     f, b = ctypes.c_int(0), ctypes.c_int(0)
-    check(L.admm_query_grouped_paths(M, N, int(bool(iso)), kh, int(planes), int(groups), mode, int(flags),
+    check(L.admm_query_grouped_paths(M, N, iso_code(iso), kh, int(planes), int(groups), mode, int(flags),
                                      int(want_hbar), int(want_rho), ctypes.byref(f), ctypes.byref(b)))
     return L.admm_path_name(f.value).decode(), (L.admm_path_name(b.value).decode() if b.value else None)
 
@@ -292,7 +315,7 @@ def query_paths(M, N, iso=False, kh=0, mode=MODE_FORWARD, flags=0, want_hbar=Fal
     of `planes` = P * B planes (0: no plane-count rule, OPT_MIN_PLANES)."""
     L = load()
     f, b = ctypes.c_int(0), ctypes.c_int(0)
-    check(L.admm_query_paths(M, N, int(iso), kh, int(planes), mode, flags, int(want_hbar), int(want_rho),
+    check(L.admm_query_paths(M, N, iso_code(iso), kh, int(planes), mode, flags, int(want_hbar), int(want_rho),
                              ctypes.byref(f), ctypes.byref(b)))
     return L.admm_path_name(f.value).decode(), (L.admm_path_name(b.value).decode() if b.value else None)
 
@@ -300,7 +323,7 @@ def query_paths(M, N, iso=False, kh=0, mode=MODE_FORWARD, flags=0, want_hbar=Fal
 def forward_schedule(M, N, iso=False, kh=0, planes=1):
     """admm_query_forward_schedule: (planes per launch, streams) of a forward over `planes` planes."""
     c, n = ctypes.c_longlong(0), ctypes.c_int(0)
-    check(load().admm_query_forward_schedule(M, N, int(iso), kh, int(planes), ctypes.byref(c), ctypes.byref(n)))
+    check(load().admm_query_forward_schedule(M, N, iso_code(iso), kh, int(planes), ctypes.byref(c), ctypes.byref(n)))
     return c.value, n.value
 
 

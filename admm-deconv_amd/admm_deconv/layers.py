@@ -94,6 +94,12 @@ def glorot_uniform(*dims_julia, rng=None):
     return (a * np.float32(math.sqrt(24.0 / (fi + fo)))).astype(np.float32)
 
 
+def _iso_bool(iso):
+    if isinstance(iso, str):
+        raise ValueError(f'iso must be False, True or "plane" (got {iso!r})')
+    return bool(iso)
+
+
 class Admm:
     """Shared state and forward of the four ADMM layer types (`Admm` union, deconv_admm.jl:212)."""
     TRAINABLE: tuple = ()
@@ -108,7 +114,8 @@ class Admm:
         self.lam = as_t(lam)
         self.rho = as_t(rho)
         self.iters = int(iters)
-        self.iso = bool(iso)
+        # False, True (the reference's batch-coupled block-thresholding) or "plane" (isotropic TV per image plane)
+        self.iso = "plane" if isinstance(iso, str) and iso == "plane" else _iso_bool(iso)
         self.creg = float(creg)
         # torch.distributed group the batch is sharded over (isotropic prox: the pixelnorm spans the
         # whole sharded batch, see ops.tvd_fft); None = this process holds the whole batch
@@ -158,7 +165,7 @@ class Admm:
 
     def __repr__(self):
         k = tuple(reversed(self.weight.shape[-2:])) if self.weight.numel() else ()
-        return f"{type(self).__name__}({k}, {self.iters}, iso={self.iso})"
+        return f"{type(self).__name__}({k}, {self.iters}, iso={self.iso!r})"
 
 
 def _psf(k, init, groups, rng):
@@ -272,6 +279,8 @@ class Parallel:
             return False
         Ls = self.layers
         if not all(isinstance(L, Admm) for L in Ls):
+            return False
+        if any(L.iso == "plane" for L in Ls):   # no one-grid form: the branches run on their own streams
             return False
         K, iso = Ls[0].iters, Ls[0].iso
         # isotropic: its one-grid solve is a launch per iteration either way.  Up to ISO_MERGE_MAX_PLANES planes in

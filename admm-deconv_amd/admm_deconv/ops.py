@@ -120,8 +120,14 @@ def _make_reducer(workspace, group):
     return _lib.BatchReducer(fn, None), fn
 
 
+def _iso_arg(isotropic):
+    """`isotropic` as the entry points carry it on: "plane" or a bool (one mapping to the C code, _lib.iso_code)."""
+    return "plane" if _lib.iso_code(isotropic) == _lib.ISO_PLANE else bool(isotropic)
+
+
 def _sharded(isotropic, group):
-    if group is None or not isotropic:
+    # only the batch-coupled prox crosses shards (anisotropic and "plane": planes are independent, group is ignored)
+    if group is None or _lib.iso_code(isotropic) != _lib.ISO_BATCH:
         return False
     import torch.distributed as dist
     return dist.is_initialized() and dist.get_world_size(group) > 1
@@ -205,7 +211,7 @@ def _forward_raw(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, out=Non
     if _on_device(lam, rho):
         dv = _DevScalars(lam, rho, y.device, stream)
         _lib.check(_lib.load().admm_tvd_forward_dev_f32(
-            y4.data_ptr(), out.data_ptr(), M, N, P, B, hp, kh, kw, *dv.ptrs, int(bool(isotropic)), int(maxit),
+            y4.data_ptr(), out.data_ptr(), M, N, P, B, hp, kh, kw, *dv.ptrs, _lib.iso_code(isotropic), int(maxit),
             ws_ptr, ws_len, s_handle, ctypes.byref(red) if red is not None else None))
     elif red is not None:
         _lib.check(_lib.load().admm_tvd_forward_sharded_f32(
@@ -214,7 +220,7 @@ def _forward_raw(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, out=Non
     else:
         _lib.check(_lib.load().admm_tvd_forward_f32(
             y4.data_ptr(), out.data_ptr(), M, N, P, B, hp, kh, kw, _scalar(lam, "lambda"), _scalar(rho, "rho"),
-            int(bool(isotropic)), int(maxit), ws_ptr, ws_len, s_handle))
+            _lib.iso_code(isotropic), int(maxit), ws_ptr, ws_len, s_handle))
     del keep
     return out.reshape(shape)
 
@@ -284,7 +290,7 @@ def tvd_fft_backward(y, x_bar, lam, rho=1.0, h=None, isotropic=False, maxit=100,
     scal = torch.zeros(2, dtype=torch.float32, device=y.device)
     head = (y4.data_ptr(), xb.data_ptr(), y_bar.data_ptr() if need_y else None, h_bar.data_ptr() if want_h else None, scal.data_ptr(),
             scal.data_ptr() + 4 if need_rho else None, M, N, P, B, None if hb is None else hb.data_ptr(), kh, kw)
-    tail = (int(bool(isotropic)), int(maxit), x.data_ptr(), ws_ptr, ws_len, s_handle)
+    tail = (_lib.iso_code(isotropic), int(maxit), x.data_ptr(), ws_ptr, ws_len, s_handle)
     red, keep = _make_reducer(workspace, group) if _sharded(isotropic, group) else (None, None)
     L = _lib.load()
     if dv is not None:
@@ -321,7 +327,7 @@ def tvd_fft_record(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, need_
     rec.dv, rec.lam, rec.rho = _scalars_for(lam, rho, y.device, stream)
     kw, kh = (0, 0) if hb is None else hb.shape
     rec.want_h = bool(need_h and hb is not None)
-    rec.y4, rec.hb, rec.shape, rec.iso, rec.maxit, rec.group = y4, hb, shape, bool(isotropic), int(maxit), group
+    rec.y4, rec.hb, rec.shape, rec.iso, rec.maxit, rec.group = y4, hb, shape, _iso_arg(isotropic), int(maxit), group
     rec.dims = (M, N, P, B, kh, kw)
     rec.flags = (_lib.REC_HBAR if rec.want_h else 0) | (0 if need_rho else _lib.REC_MASKS)
     nbytes = _lib.backward_workspace_bytes(M, N, P, B, kh, kw, isotropic, maxit, rec.flags)
@@ -329,7 +335,7 @@ def tvd_fft_record(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, need_
     x = torch.empty_like(y4)
     red, keep = _make_reducer(rec.workspace, group) if _sharded(isotropic, group) else (None, None)
     head = (y4.data_ptr(), x.data_ptr(), M, N, P, B, None if hb is None else hb.data_ptr(), kh, kw)
-    tail = (int(rec.iso), rec.maxit, rec.flags, ws_ptr, ws_len, s_handle,
+    tail = (_lib.iso_code(rec.iso), rec.maxit, rec.flags, ws_ptr, ws_len, s_handle,
             ctypes.byref(red) if red is not None else None)
     L = _lib.load()
     if rec.dv is not None:
@@ -362,7 +368,7 @@ def tvd_fft_backward_recorded(rec, x, x_bar, *, stream=None, need_y=True, need_r
     red, keep = _make_reducer(ws, rec.group) if _sharded(rec.iso, rec.group) else (None, None)
     head = (y4.data_ptr(), xb.data_ptr(), y_bar.data_ptr() if need_y else None, h_bar.data_ptr() if rec.want_h else None, scal.data_ptr(),
             scal.data_ptr() + 4 if need_rho else None, M, N, P, B, None if hb is None else hb.data_ptr(), kh, kw)
-    tail = (int(rec.iso), rec.maxit, x4.data_ptr(), ws_ptr, ws_len, s_handle,
+    tail = (_lib.iso_code(rec.iso), rec.maxit, x4.data_ptr(), ws_ptr, ws_len, s_handle,
             ctypes.byref(red) if red is not None else None)
     L = _lib.load()
     if rec.dv is not None:
@@ -422,7 +428,11 @@ def tvd_fft(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, out=None, wo
     group: torch.distributed group the batch is sharded over (each rank passes its own slice).  The
     isotropic prox's pixelnorm then spans the whole sharded batch (one M x N all-reduce per
     iteration), so every rank gets its slice of the unsharded result; ignored for the anisotropic
-    prox, whose planes are independent.
+    prox and for isotropic="plane", whose planes are independent.
+    isotropic: False (anisotropic TV), True (the reference's block-thresholding, whose pixel norm runs over every
+    plane of the call: a plane's result depends on its batch) or "plane" (isotropic TV of each image plane on its
+    own, sum over pixels of sqrt(dx^2 + dy^2): the result of a plane does not depend on the batch; 2-pass /
+    runtime-length kernels; zero norm gives a zero factor, never NaN).
     scalars: optional host (lambda, rho) equal to the values of tensor lam / rho, used instead of the
     device values (gradients still flow to the tensors)."""
     tensors = [t for t in (y, lam, rho, h) if isinstance(t, torch.Tensor)]
@@ -430,7 +440,7 @@ def tvd_fft(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, out=None, wo
         dev = y.device
         as_t = lambda v: v if isinstance(v, torch.Tensor) else torch.full((1,), float(v), device=dev)  # noqa: E731
         h_t = h if isinstance(h, torch.Tensor) else torch.zeros(0, device=dev)
-        return _TvdFFTFn.apply(y, as_t(lam), as_t(rho), h_t, bool(isotropic), int(maxit), group, scalars)
+        return _TvdFFTFn.apply(y, as_t(lam), as_t(rho), h_t, _iso_arg(isotropic), int(maxit), group, scalars)
     if scalars is not None:
         lam, rho = scalars
     return _forward_raw(y, lam, rho, h, isotropic, maxit, out=out, workspace=workspace, stream=stream, group=group)
@@ -447,6 +457,7 @@ def tvd_fft_state(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, state=
     the call's own lam / rho form the prox of the given state, so a warm start under other parameters is well defined.
     resid: float32 (B, P, 4) = (|r|, |d|, pri, dual) per plane, the norms of the stopping rule (tvd_fft_tol).
     Neither `y` nor `state` is modified.  Not differentiable: ValueError when an input requires grad under autograd."""
+    _lib.no_plane_mode(isotropic, "tvd_fft_state")
     tensors = [t for t in (y, lam, rho, h, state) if isinstance(t, torch.Tensor)]
     if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
         raise ValueError("tvd_fft_state is not differentiable (use tvd_fft, or call it under torch.no_grad())")
@@ -484,6 +495,7 @@ def tvd_fft_tol(y, lam, rho=1.0, h=None, isotropic=False, maxit=100, *, eps_abs=
         |r| <= sqrt(2 M N) eps_abs + eps_rel pri   and   |d| <= sqrt(M N) eps_abs + eps_rel dual
     (resid of tvd_fft_state).  Returns (x, state, iters, resid); iters is the total run.  The residuals are read back
     once per block -- the call's only host synchronisation.  `state`: an optional warm start."""
+    _lib.no_plane_mode(isotropic, "tvd_fft_tol")
     maxit, check_every = int(maxit), int(check_every)
     if maxit < 1 or check_every < 1:
         raise ValueError("tvd_fft_tol: maxit and check_every must be >= 1")
@@ -541,7 +553,8 @@ def tvd_fft_grouped(y, lam, rho, h, isotropic=False, maxit=100, *, out=None, wor
          (B * P values: per plane, B: per image, P: per channel, 1: one group; with B == P, B values name neither and
          are refused: give B * P).
     lam, rho: floats, or tensors of 1 or gb * gp elements (group order b * gp + p); they stay on the device.
-    isotropic: the batch coupling of the reference is kept over ALL planes, so lam and rho must have one element.
+    isotropic: True keeps the batch coupling of the reference over ALL planes, so lam and rho must have one element;
+    "plane" (isotropic TV per plane) takes per-group lam and rho like the anisotropic prox.
     Not differentiable itself: tvd_fft_grouped_grad is the entry with the grouped adjoint."""
     _check_y(y, "tvd_fft_grouped", (4,), "4-D (B, P, N, M)")
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (y, h, lam, rho)):
@@ -558,7 +571,7 @@ def tvd_fft_grouped(y, lam, rho, h, isotropic=False, maxit=100, *, out=None, wor
     _record_streams(stream, y.device, lt, rt, hbuf)
     _lib.check(_lib.load().admm_tvd_forward_grouped_dev_f32(
         y4.data_ptr(), out.data_ptr(), M, N, P, B, gb, gp, hp, kh, kw, lt.data_ptr(), rt.data_ptr(), nparam,
-        int(bool(isotropic)), int(maxit), ws_ptr, ws_len, s_handle))
+        _lib.iso_code(isotropic), int(maxit), ws_ptr, ws_len, s_handle))
     return out
 
 
@@ -612,6 +625,7 @@ class GroupedRecording:
 
 def _grouped_adjoint_args(y, lam, rho, h, isotropic, maxit, need_h):
     """A grouped adjoint call's arguments resolved (_grouped_args) into a GroupedRecording that holds no workspace yet."""
+    _lib.no_plane_mode(isotropic, "the grouped adjoint")
     g = GroupedRecording()
     g.y4, g.hb, g.lt, g.rt, g.nparam, g.gb, g.gp = _grouped_args(y, lam, rho, h)
     g.iso, g.maxit, g.want_h, g.workspace = bool(isotropic), int(maxit), bool(need_h and g.hb is not None), None
@@ -721,6 +735,7 @@ def tvd_fft_grouped_grad(y, lam, rho, h, isotropic=False, maxit=100):
     reverse sweep (the dim-2 spectra for h_bar are recorded only if h requires grad; rho_bar and y_bar are formed only
     if wanted).  Gradients come back in the shapes given: h.grad (gb, gp, kw, kh); a 1-element lam next to per-group
     rho gets the sum over the groups; a Python float gets none.  Without grad it is the plain call."""
+    _lib.no_plane_mode(isotropic, "tvd_fft_grouped_grad")
     ts = [t for t in (y, lam, rho, h) if isinstance(t, torch.Tensor)]
     if not (torch.is_grad_enabled() and any(t.requires_grad for t in ts)):
         return tvd_fft_grouped(y, lam, rho, h, isotropic, maxit)
@@ -732,9 +747,9 @@ def tvd_fft_grouped_grad(y, lam, rho, h, isotropic=False, maxit=100):
 
 def multi_supported(y, isotropic=False, psf=None, group=None):
     """Whether the one-grid multi-branch solve (admm_tvd_forward_multi_dev_f32) covers this input: the fused
-    256 x 256 kernels (anisotropic, or isotropic with the fused reverse sweep on), no PSF, one process
-    holding the batch, and the fused option on."""
-    return (isinstance(y, torch.Tensor) and y.is_cuda and y.dtype == torch.float32 and y.dim() == 4
+    256 x 256 kernels (anisotropic, or isotropic with the fused reverse sweep on; never isotropic="plane"), no PSF,
+    one process holding the batch, and the fused option on."""
+    return (_lib.iso_code(isotropic) != _lib.ISO_PLANE and isinstance(y, torch.Tensor) and y.is_cuda and y.dtype == torch.float32 and y.dim() == 4
             and y.shape[-1] == MULTI_M and y.shape[-2] == MULTI_N
             and (not isotropic or _lib.get_option("FUSED_ADJ") == 1)
             and (psf is None or psf.numel() == 0) and group is None and _lib.get_option("FUSED") == 1)
@@ -758,6 +773,7 @@ def tvd_fft_multi(y, lams, rhos, maxit=100, *, out=None, record=False, need_rho=
     a MultiRecording for tvd_fft_multi_backward_recorded (need_rho=False: only the ST branches are kept).
     isotropic=True: the BT prox (ops.jl:6,10), each branch's norm over its own planes; its recording never
     gives rho_bar (the fused isotropic sweep, plane_iso.hip)."""
+    _lib.no_plane_mode(isotropic, "tvd_fft_multi")
     if not multi_supported(y, isotropic):
         raise ValueError("tvd_fft_multi: y must be a float32 (B, P, 256, 256) ROCm tensor (fused options on)")
     if record and isotropic and need_rho:
@@ -845,6 +861,7 @@ class _TvdFFTMultiFn(torch.autograd.Function):
 
 def tvd_fft_multi_grad(y, lams, rhos, maxit=100, isotropic=False):
     """tvd_fft_multi under autograd when y or any lam / rho tensor requires grad (else the plain call)."""
+    _lib.no_plane_mode(isotropic, "tvd_fft_multi_grad")
     ts = [t for t in (y, *lams, *rhos) if isinstance(t, torch.Tensor)]
     if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
         dev = y.device

@@ -81,9 +81,14 @@ int check_shape(int M, int N, int P, int B, int kh, int kw, int iso) {
         return fail(ADMM_E_UNSUPPORTED, "this build supports 2<=M<=%d, 2<=N<=%d (got M=%d N=%d)", kGenMax, kGenMax, M, N);
     if (kh > M || kw > N)
         return fail(ADMM_E_UNSUPPORTED, "PSF %dx%d larger than the image (kh<=M, kw<=N required, as pad_constant in ops.jl:25)", kh, kw);
-    if (iso && (size_t)P * B > 65535)
+    if (iso_batch(iso) && (size_t)P * B > 65535)
         return fail(ADMM_E_UNSUPPORTED, "isotropic prox couples the batch: at most 65535 planes per call");
     return ADMM_OK;
+}
+
+int no_plane_mode(int iso, const char* who) {
+    if (!iso_plane(iso)) return ADMM_OK;
+    return fail(ADMM_E_UNSUPPORTED, "%s has no per-plane isotropic form (iso = ADMM_ISO_PLANE)", who);
 }
 
 }  // namespace admm_capi
@@ -94,13 +99,15 @@ extern "C" {
 
 int admm_abi_version(void) { return ADMM_ABI_VERSION; }
 
+int admm_iso_plane_supported(void) { return 1; }
+
 const char* admm_last_error(void) { return g_err.c_str(); }
 
 int admm_tvd_workspace_bytes(int M, int N, int P, int B, int kh, int kw, int iso, size_t* out_bytes) {
     if (!out_bytes) return fail(ADMM_E_INVALID, "out_bytes is NULL");
     int rc = check_shape(M, N, P, B, kh, kw, iso);
     if (rc) return rc;
-    *out_bytes = forward_ws_bytes(M, N, (size_t)P * B, kh, iso != 0);
+    *out_bytes = forward_ws_bytes(M, N, (size_t)P * B, kh, iso);
     return ADMM_OK;
 }
 
@@ -185,7 +192,8 @@ float g_dummy_scalar = 0.f;   // stands for "device-resident scalars" when a tag
 RecTag make_tag(const Call& c, bool want_h, bool masks) {
     RecTag t;
     std::memset(&t, 0, sizeof(t));
-    t.M = c.M, t.N = c.N, t.P = c.P, t.B = c.B, t.kh = c.kh, t.kw = c.kw, t.iso = c.iso != 0, t.maxit = c.maxit;
+    t.M = c.M, t.N = c.N, t.P = c.P, t.B = c.B, t.kh = c.kh, t.kw = c.kw, t.maxit = c.maxit;
+    t.iso = iso_plane(c.iso) ? ADMM_ISO_PLANE : c.iso != 0;   // the mode: no prox replays another's recording
     t.want_h = want_h, t.masks = masks;
     t.nbr = 1;
     t.dev_scalars = c.sc.lam != nullptr;
@@ -249,10 +257,10 @@ hipStream_t lib_stream(int i) {
 }
 
 // forward workspace: one chunk layout, or one per stream of the MALL-resident schedule
-size_t forward_ws_bytes(int M, int N, size_t planes, int kh, bool iso, const PathPlan* plp) {
-    const PathPlan pl = plp ? *plp : plan_paths({M, N, iso, kh > 0, ADMM_MODE_FORWARD, 0, false, false, planes});
-    const ChunkPlan cp = forward_chunks(M, N, planes, iso, pl.fwd);
-    const size_t one = make_layout(M, N, cp.chunk, kh > 0, iso).total;
+size_t forward_ws_bytes(int M, int N, size_t planes, int kh, int iso, const PathPlan* plp) {
+    const PathPlan pl = plp ? *plp : plan_paths(path_in(M, N, iso, kh > 0, ADMM_MODE_FORWARD, 0, false, false, planes));
+    const ChunkPlan cp = forward_chunks(M, N, planes, iso_batch(iso), pl.fwd, iso_plane(iso));
+    const size_t one = make_layout(M, N, cp.chunk, kh > 0, iso_batch(iso)).total;
     return cp.streams > 1 ? (size_t)cp.streams * align_up(one) : one;
 }
 
@@ -289,7 +297,8 @@ int check_call(const Call& c, int phases, const Grads* g, int rec_flags = 0) {
         if (!c.sc.lam || !c.sc.rho) return fail(ADMM_E_INVALID, "%s: lambda and rho must be device pointers", who);
         if (c.nparam != 1 && c.nparam != c.groups())
             return fail(ADMM_E_INVALID, "%s: nparam must be 1 or the group count %d (got %d)", who, c.groups(), c.nparam);
-        if (c.iso && c.nparam > 1)
+        if (phases && no_plane_mode(c.iso, "the grouped adjoint")) return ADMM_E_UNSUPPORTED;
+        if (iso_batch(c.iso) && c.nparam > 1)
             return fail(ADMM_E_UNSUPPORTED, "%s: the isotropic prox is one BT factor map per batch, so it takes one "
                                             "(lambda, rho) pair (nparam = 1), got %d", who, c.nparam);
         if (rec_flags & ~(ADMM_REC_HBAR | ADMM_REC_MASKS)) return fail(ADMM_E_INVALID, "%s: unknown rec_flags 0x%x", who, rec_flags);
@@ -308,7 +317,7 @@ int check_call(const Call& c, int phases, const Grads* g, int rec_flags = 0) {
 // a single solve's descriptor: h == NULL is "no PSF"; the reducer acts on the isotropic prox only
 Call single_call(Call c) {
     if (c.h == nullptr) c.kh = c.kw = 0;
-    c.red = (c.iso && c.red && c.red->fn) ? c.red : nullptr;
+    c.red = (iso_batch(c.iso) && c.red && c.red->fn) ? c.red : nullptr;
     return c;
 }
 
@@ -316,16 +325,16 @@ int forward_impl(const Call& c) {
     int rc = check_call(c, 0, nullptr);
     if (rc) return rc;
     const int M = c.M, N = c.N;
-    const bool iso = c.iso != 0;
+    const bool iso = iso_batch(c.iso);
     const size_t planes = c.planes();
     // a sharded isotropic solve plans without the plane-count rule: every shard must take the same path, since
     // the fused and 2-pass kernels hand the reducer their sum maps in different layouts (lane-native float2 vs
     // natural), and uneven shards can fall on either side of a threshold
-    const PathPlan pl = plan_paths({M, N, iso, c.kh > 0, ADMM_MODE_FORWARD, 0, false, false, c.red ? 0 : planes});
-    const ChunkPlan cp = forward_chunks(M, N, planes, iso, pl.fwd);
+    const PathPlan pl = plan_paths(path_in(M, N, c.iso, c.kh > 0, ADMM_MODE_FORWARD, 0, false, false, c.red ? 0 : planes));
+    const ChunkPlan cp = forward_chunks(M, N, planes, iso, pl.fwd, iso_plane(c.iso));
     const size_t chunk = cp.chunk;   // an isotropic batch is one chunk
     const Layout lay = make_layout(M, N, chunk, c.kh > 0, iso);
-    rc = check_ws(c.workspace, c.workspace_bytes, forward_ws_bytes(M, N, planes, c.kh, iso, &pl));
+    rc = check_ws(c.workspace, c.workspace_bytes, forward_ws_bytes(M, N, planes, c.kh, c.iso, &pl));
     if (rc) return rc;
     rec_forget(c.workspace);   // whatever was recorded there is overwritten now
     const hipStream_t s0 = reinterpret_cast<hipStream_t>(c.stream);
@@ -404,13 +413,13 @@ Layout make_grouped_layout(int M, int N, size_t planes, int groups, bool psf, bo
 int forward_grouped(const Call& c) {
     int rc = check_call(c, 0, nullptr);
     if (rc) return rc;
-    const Layout lay = make_grouped_layout(c.M, c.N, c.planes(), c.groups(), c.kh > 0, c.iso != 0);
+    const Layout lay = make_grouped_layout(c.M, c.N, c.planes(), c.groups(), c.kh > 0, iso_batch(c.iso));
     rc = check_ws(c.workspace, c.workspace_bytes, lay.total);
     if (rc) return rc;
     rec_forget(c.workspace);
     Launcher ln{reinterpret_cast<hipStream_t>(c.stream), g_prof.on, {}};
     rc = run_forward(ln, c, static_cast<unsigned char*>(c.workspace), lay, Traj{},
-                     plan_grouped(c.M, c.N, c.iso != 0, c.planes()));
+                     plan_grouped(c.M, c.N, iso_batch(c.iso), c.planes(), iso_plane(c.iso)));
     const int rc2 = ln.finish();
     return rc ? rc : rc2;
 }
@@ -437,6 +446,7 @@ int check_state_shape(int M, int N, int P, int B, int kh, int kw, int iso) {
 }
 
 int forward_state(Call c, const float* state_in, float* state_out, float* resid_out) {
+    if (no_plane_mode(c.iso, "the state call")) return ADMM_E_UNSUPPORTED;
     int rc = check_state_shape(c.M, c.N, c.P, c.B, c.kh, c.kw, c.iso);
     if (rc) return rc;
     if (c.kh > 0 && !c.h) return fail(ADMM_E_INVALID, "state call: h is NULL with a %d x %d PSF", c.kh, c.kw);
@@ -462,7 +472,7 @@ int forward_state(Call c, const float* state_in, float* state_out, float* resid_
 BwdLayout make_grouped_bwd_layout(const Call& c, bool want_h) {
     const int M = c.M, N = c.N;
     const size_t planes = c.planes(), G = (size_t)c.groups(), ntaps = (size_t)c.kh * c.kw;
-    const bool psf = c.kh > 0, hq = want_h && psf, iso = c.iso != 0;
+    const bool psf = c.kh > 0, hq = want_h && psf, iso = iso_batch(c.iso);
     BwdLayout b = make_bwd_layout(M, N, planes, c.kh, c.kw, c.maxit, want_h, iso);
     Carver cv{align_up(b.total)};
     take_group_tables(cv, b.f, M, N, G, psf);
@@ -491,7 +501,7 @@ BwdLayout make_grouped_bwd_layout(const Call& c, bool want_h) {
 int run_backward(int phases, int rec_flags, const Call& c, const Grads& g) {
     int rc = check_call(c, phases, &g, rec_flags);
     if (rc) return rc;
-    const bool iso = c.iso != 0;
+    const bool iso = iso_batch(c.iso);
     PathPlan plan;
     BwdLayout bl;
     RecTag tag;
@@ -505,8 +515,8 @@ int run_backward(int phases, int rec_flags, const Call& c, const Grads& g) {
         } else {
             const int pflags = phases != 2 ? rec_flags : (g.h_bar ? ADMM_REC_HBAR : 0) | (masks ? ADMM_REC_MASKS : 0);
             // sharded (c.red): no plane-count rule, so that every shard records and sweeps in one layout (forward_impl)
-            plan = plan_paths({c.M, c.N, iso, c.kh > 0, phases == 3 ? ADMM_MODE_BACKWARD : ADMM_MODE_RECORD, pflags,
-                               g.h_bar != nullptr, g.rho_bar != nullptr, c.red ? 0 : c.planes()});
+            plan = plan_paths(path_in(c.M, c.N, c.iso, c.kh > 0, phases == 3 ? ADMM_MODE_BACKWARD : ADMM_MODE_RECORD, pflags,
+                                      g.h_bar != nullptr, g.rho_bar != nullptr, c.red ? 0 : c.planes()));
             bl = make_bwd_layout(c.M, c.N, c.planes(), c.kh, c.kw, c.maxit, plan.want_h, iso, plan.masks && !iso);
         }
         tag = make_tag(c, plan.want_h, plan.masks);
@@ -742,8 +752,8 @@ int admm_tvd_backward_workspace_bytes(int M, int N, int P, int B, int kh, int kw
     if (rc) return rc;
     if (maxit < 0) return fail(ADMM_E_INVALID, "maxit must be >= 0");
     if ((size_t)P * B > 65535) return fail(ADMM_E_UNSUPPORTED, "the adjoint takes at most 65535 planes per call (split the batch)");
-    const PathPlan pl = plan_paths({M, N, iso != 0, kh > 0, ADMM_MODE_RECORD, want_hbar, false, false, (size_t)P * B});
-    *out_bytes = make_bwd_layout(M, N, (size_t)P * B, kh, kw, maxit, pl.want_h, iso != 0, pl.masks && !iso).total;
+    const PathPlan pl = plan_paths(path_in(M, N, iso, kh > 0, ADMM_MODE_RECORD, want_hbar, false, false, (size_t)P * B));
+    *out_bytes = make_bwd_layout(M, N, (size_t)P * B, kh, kw, maxit, pl.want_h, iso_batch(iso), pl.masks && !iso).total;
     return ADMM_OK;
 }
 
@@ -900,7 +910,7 @@ int admm_tvd_grouped_workspace_bytes(int M, int N, int P, int B, int gb, int gp,
     if (!out_bytes) return fail(ADMM_E_INVALID, "out_bytes is NULL");
     const int rc = check_grouped(M, N, P, B, gb, gp, kh, kw, iso);
     if (rc) return rc;
-    *out_bytes = make_grouped_layout(M, N, (size_t)P * B, gb * gp, kh > 0, iso != 0).total;
+    *out_bytes = make_grouped_layout(M, N, (size_t)P * B, gb * gp, kh > 0, iso_batch(iso)).total;
     return ADMM_OK;
 }
 
@@ -920,6 +930,7 @@ int admm_tvd_grouped_backward_workspace_bytes(int M, int N, int P, int B, int gb
     if (!out_bytes) return fail(ADMM_E_INVALID, "out_bytes is NULL");
     const int rc = check_grouped(M, N, P, B, gb, gp, kh, kw, iso);
     if (rc) return rc;
+    if (no_plane_mode(iso, "the grouped adjoint")) return ADMM_E_UNSUPPORTED;
     if (maxit < 0) return fail(ADMM_E_INVALID, "maxit must be >= 0");
     const PathPlan pl = plan_grouped_adjoint(M, N, iso != 0, kh > 0, (size_t)P * B, (rec_flags & ADMM_REC_HBAR) != 0);
     // the larger of a pair per group (the larger (rho_bar, tau_bar) partial block) and one pair (more rows per part)
@@ -961,6 +972,7 @@ int admm_tvd_state_workspace_bytes(int M, int N, int P, int B, int kh, int kw, i
     if (!out_bytes) return fail(ADMM_E_INVALID, "out_bytes is NULL");
     const int rc = check_state_shape(M, N, P, B, kh, kw, iso);
     if (rc) return rc;
+    if (no_plane_mode(iso, "the state call")) return ADMM_E_UNSUPPORTED;
     // (the plain forward of the same arguments fits too: its MALL chunk schedule never needs more than the whole batch)
     *out_bytes = std::max(make_state_layout(M, N, (size_t)P * B, kh > 0, iso != 0).total,
                           forward_ws_bytes(M, N, (size_t)P * B, kh, iso != 0));

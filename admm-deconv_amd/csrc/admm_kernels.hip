@@ -564,9 +564,29 @@ __global__ __launch_bounds__(NT) void column_kernel(const float2* src, float2* d
 }
 
 // ----------------------------------------------------------------------------------------------
-// LINE pass (iterations 1..K-1): T output lines + 1 halo line on each side.
+// Per-plane block soft-thresholding (isotropic TV of one image plane, ADMM_ISO_PLANE): the prox of a pixel's own
+// 2-vector s = (s0, s1).  n = |s|, f = max(1 - tau / n, 0) for n > tau and 0 otherwise -- n = 0 gives f = 0, never the
+// NaN of the reference's 0 / 0 at tau = 0.  z = f s, u = s - f s, w = z - u = (2f - 1) s.  Every kernel of the mode
+// (forward: u_{k-1} re-formed from s_{k-1} and w from s_k; the reverse sweeps) takes f from bt_factor alone.
 // ----------------------------------------------------------------------------------------------
-template <int L, int T, int NT = kThreads, bool GRP = false>
+// (one v_sqrt_f32 and one v_rcp_f32 per factor, 1 ulp each.  The libm sqrtf, with its range scaling and correction
+// step, put the 512-point line pass 15 % over the anisotropic one where these two put it 4.6 % over, DESIGN.md s5;
+// f does not need the last bit)
+__device__ __forceinline__ float bt_norm(float s0, float s1) { return __builtin_amdgcn_sqrtf(fmaf(s0, s0, s1 * s1)); }
+__device__ __forceinline__ float bt_factor_of(float n, float tau) {
+    return n > tau ? fmaxf(1.0f - tau * __builtin_amdgcn_rcpf(n), 0.0f) : 0.0f;
+}
+__device__ __forceinline__ float bt_factor(float s0, float s1, float tau) { return bt_factor_of(bt_norm(s0, s1), tau); }
+__device__ __forceinline__ float bt_u(float s, float f) { return fmaf(-f, s, s); }
+__device__ __forceinline__ float bt_w(float s, float f) { return ((f + f) - 1.0f) * s; }
+
+// ----------------------------------------------------------------------------------------------
+// LINE pass (iterations 1..K-1): T output lines + 1 halo line on each side.
+// BT: the per-plane block-threshold prox in place of ST.  The factor of a pixel needs both channels, so the halo
+// line t = T (whose channel 0 feeds D^T) also loads s_old channel 1 and forms s1 from the x line already in LDS;
+// it stores nothing for it.
+// ----------------------------------------------------------------------------------------------
+template <int L, int T, int NT = kThreads, bool GRP = false, bool BT = false>
 __device__ __forceinline__ void line_body(XBlk xb, const float2* __restrict__ spec1, float2* __restrict__ spec0,
                                           const float* __restrict__ s_old, float* __restrict__ s_new,
                                           const float* __restrict__ hty, const float2* __restrict__ twM, int N,
@@ -616,7 +636,7 @@ __device__ __forceinline__ void line_body(XBlk xb, const float2* __restrict__ sp
             pre1[it] = pre0[it];
             if (!s_zero && idx < NE) {
                 pre0[it] = *reinterpret_cast<const float4*>(so + off);
-                if (t < T) pre1[it] = *reinterpret_cast<const float4*>(so + MN + off);
+                if (BT || t < T) pre1[it] = *reinterpret_cast<const float4*>(so + MN + off);
             }
         }
     };
@@ -679,6 +699,32 @@ __device__ __forceinline__ void line_body(XBlk xb, const float2* __restrict__ sp
             const float4 xc = *reinterpret_cast<const float4*>(x + (t + 1) * M + i);
             const float4 xp = *reinterpret_cast<const float4*>(x + t * M + i);
             const float4 u0 = pre0[it];
+            if constexpr (BT) {
+                const float xl = x[(t + 1) * M + ((i - 1) & (M - 1))];
+                const float4 u1 = pre1[it];
+                const float fx = bt_factor(u0.x, u1.x, tau), fy = bt_factor(u0.y, u1.y, tau);
+                const float fz = bt_factor(u0.z, u1.z, tau), fw = bt_factor(u0.w, u1.w, tau);
+                float4 s0, s1;
+                s0.x = (xc.x - xp.x) + bt_u(u0.x, fx);
+                s0.y = (xc.y - xp.y) + bt_u(u0.y, fy);
+                s0.z = (xc.z - xp.z) + bt_u(u0.z, fz);
+                s0.w = (xc.w - xp.w) + bt_u(u0.w, fw);
+                s1.x = (xc.x - xl) + bt_u(u1.x, fx);
+                s1.y = (xc.y - xc.x) + bt_u(u1.y, fy);
+                s1.z = (xc.z - xc.y) + bt_u(u1.z, fz);
+                s1.w = (xc.w - xc.z) + bt_u(u1.w, fw);
+                const float gx = bt_factor(s0.x, s1.x, tau), gy = bt_factor(s0.y, s1.y, tau);
+                const float gz = bt_factor(s0.z, s1.z, tau), gw = bt_factor(s0.w, s1.w, tau);
+                *reinterpret_cast<float4*>(W0 + t * M + i) =
+                    make_float4(bt_w(s0.x, gx), bt_w(s0.y, gy), bt_w(s0.z, gz), bt_w(s0.w, gw));
+                if (t < T) {
+                    *reinterpret_cast<float4*>(W1 + t * M + i) =
+                        make_float4(bt_w(s1.x, gx), bt_w(s1.y, gy), bt_w(s1.z, gz), bt_w(s1.w, gw));
+                    *reinterpret_cast<float4*>(sn + off) = s0;
+                    *reinterpret_cast<float4*>(sn + MN + off) = s1;
+                }
+                continue;
+            }
             float4 s0;
             s0.x = (xc.x - xp.x) + clipf(u0.x, tau);
             s0.y = (xc.y - xp.y) + clipf(u0.y, tau);
@@ -761,6 +807,16 @@ __global__ __launch_bounds__(NT) void line_kernel(const float2* __restrict__ spe
                                                   const float* __restrict__ hty, const float2* __restrict__ twM, int N,
                                                   const float* __restrict__ prm, int s_zero, Branches br = kOneSolve) {
     line_body<L, T, NT, GRP>(xcd_block(), spec1, spec0, s_old, s_new, hty, twM, N, prm, s_zero, br);
+}
+
+// the per-plane block-threshold line pass (ADMM_ISO_PLANE): instantiated behind every other 2-pass kernel
+// (admm_launch.hip launch_line_bt)
+template <int L, int T, int NT = kThreads, bool GRP = false>
+__global__ __launch_bounds__(NT) void line_bt_kernel(const float2* __restrict__ spec1, float2* __restrict__ spec0,
+                                                     const float* __restrict__ s_old, float* __restrict__ s_new,
+                                                     const float* __restrict__ hty, const float2* __restrict__ twM, int N,
+                                                     const float* __restrict__ prm, int s_zero, Branches br = kOneSolve) {
+    line_body<L, T, NT, GRP, true>(xcd_block(), spec1, spec0, s_old, s_new, hty, twM, N, prm, s_zero, br);
 }
 
 // ----------------------------------------------------------------------------------------------

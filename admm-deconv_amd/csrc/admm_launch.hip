@@ -196,6 +196,23 @@ int launch_line_adj_grouped(int L, int T, dim3 g, size_t lds, hipStream_t s, con
                             double* part, const float2* twM, int N, const float* prm, int first_k, int last_k, bool ln,
                             const Branches& br);
 
+// The per-plane isotropic mode's kernels (ADMM_ISO_PLANE: line_bt_kernel and admm_plane_bt.hip) are named at the end
+// of this file too.  The 2-pass launchers take launch_line's / launch_line_adj's arguments, the runtime-length ones the
+// kernels' own.
+int launch_line_bt(int L, int T, dim3 g, size_t lds, hipStream_t s, const float2* spec1, float2* spec0, const float* so,
+                   float* sn, const float2* twM, int N, const float* prm, int sz, int nt, const Branches& br);
+int launch_line_adj_bt(int L, int T, dim3 g, size_t lds, hipStream_t s, const float2* spec1, const float* sk1,
+                       const float* sk, const float* xK, const float* sb_in, float* sb_out, float* vsum, float2* spec0,
+                       double* part, const float2* twM, int N, const float* prm, int first_k, int last_k,
+                       const Branches& br);
+int launch_gen_line_upd_bt(dim3 g, size_t lds, hipStream_t s, const float* x, const float* so, float* sn, float2* spec,
+                           const float2* twM, const admm::gen::FPlan& pM, int N, int T, const float* prm, int first,
+                           const Branches& br);
+int launch_gen_line_adj_bt(dim3 g, size_t lds, hipStream_t s, const float* vb, const float* sk1, const float* sk,
+                           const float* xK, const float* sb_in, float* sb_out, float* vsum, float2* spec, double* part,
+                           const float2* twM, const admm::gen::FPlan& pM, int N, int T, const float* prm,
+                           const Branches& br);
+
 // mode: 0 = x-update C, 1 = conj(Sigma_c) (H^T), 2 = Sigma_c (H), 3 = C + save spectrum, 4 = C + accumulate Q;
 // 5 = Y_h = cs conj(Sigma_c) F y stored to yh (G NULL: Y_h = cs F y), no inverse; 6 = + yh, x C; 7 = + yh, save, x C
 // (admm_kernels.hip YH_STORE / YH_ADD: H^T y in the spectral domain); br: several branches (C per branch, br.tab_f
@@ -405,6 +422,8 @@ struct TwoPass {
     int rows;
     size_t pbs;
     int r_off;
+    // ADMM_ISO_PLANE: the anisotropic sequences with the block-threshold line update / line adjoint
+    bool bt = false;
 };
 
 TwoPass two_pass_grid(Launcher& ln, int M, int N, size_t planes, int T) {
@@ -519,6 +538,9 @@ int two_pass_forward(const TwoPass& c, const float* y, float* x_out, int maxit, 
         if (it == 1 && s0) p.so = s0;
         if (!iso) {
             rc = ln.run(ADMM_K_LINE, [&] {
+                if (c.bt)
+                    return launch_line_bt(c.L, c.Tu, c.gu, c.llds, s, c.spec1, c.spec0, p.so, p.sn, c.twM, c.N, c.prm, sz,
+                                          c.nTu, c.br);
                 return launch_line(c.L, c.Tu, c.gu, c.llds, s, c.spec1, c.spec0, p.so, p.sn, nullptr, c.twM, c.N, c.prm,
                                    sz, c.nTu, c.br);
             });
@@ -632,7 +654,7 @@ int run_forward(Launcher& ln, const Call& c, unsigned char* ws, const Layout& la
                 bool tables, size_t p0, size_t np) {
     hipStream_t s = ln.s;
     int rc = ADMM_OK;
-    const int M = c.M, N = c.N, kh = c.kh, kw = c.kw, iso = c.iso, maxit = c.maxit;
+    const int M = c.M, N = c.N, kh = c.kh, kw = c.kw, iso = iso_batch(c.iso), maxit = c.maxit;
     const size_t MN = (size_t)M * N, planes = np ? np : c.planes();
     const float* y = c.y + p0 * MN;
     float* x_out = c.x_out + p0 * MN;
@@ -715,7 +737,8 @@ int run_forward(Launcher& ln, const Call& c, unsigned char* ws, const Layout& la
                          reinterpret_cast<float2*>(v.fmap), v.spec1};
         return fused_iso_forward(ln, f, y, x_out, kh > 0, v.spec0, maxit, red, reinterpret_cast<float2*>(v.part));
     }
-    const TwoPass t = two_pass_single(ln, M, N, planes, line_T(M, N), v, br);
+    TwoPass t = two_pass_single(ln, M, N, planes, line_T(M, N), v, br);
+    t.bt = iso_plane(c.iso);
     if (path == ADMM_PATH_RESIDENT || path == ADMM_PATH_RESIDENT_ISO) {
         // power-of-two sides admm_resident.hip compiled: one workgroup per plane runs all K iterations (s_k into
         // the trajectory slots when recording, natural layout, as the 2-pass sweep reads them); H^T y from the
@@ -799,14 +822,16 @@ int run_forward_generic(Launcher& ln, const Call& c, const PlaneRange& r, const 
     namespace g = admm::gen;
     hipStream_t s = ln.s;
     int rc = ADMM_OK;
-    const int M = c.M, N = c.N, iso = c.iso, maxit = c.maxit;
+    const int M = c.M, N = c.N, iso = iso_batch(c.iso), maxit = c.maxit;
+    const bool bt = iso_plane(c.iso);
     const float* y = r.y;
     float* x_out = r.x_out;
     const size_t planes = r.planes;
     const admm_batch_reducer* red = c.red;
     const size_t MN = (size_t)M * N;
-    // (a grouped solve runs the runtime-length kernels only: they take the group offsets; a state call too)
-    const GenPass p = gen_pass(M, N, planes, opt(ADMM_OPT_SMOOTH) != 0 && br.nbr != 0 && !c.st);
+    // (a grouped solve runs the runtime-length kernels only: they take the group offsets; a state call and the
+    // per-plane isotropic mode too)
+    const GenPass p = gen_pass(M, N, planes, opt(ADMM_OPT_SMOOTH) != 0 && br.nbr != 0 && !c.st && !bt);
     const float* s0 = c.st ? c.st->in : nullptr;
     set_lds(g::line_upd_kernel, p.lup);
     set_lds(g::iso_b_kernel, p.lup);
@@ -867,6 +892,9 @@ int run_forward_generic(Launcher& ln, const Call& c, const PlaneRange& r, const 
         if (it == 1 && s0) sl.so = s0;
         if (!iso) {
             rc = ln.run(ADMM_K_LINE, [&] {
+                if (bt)
+                    return launch_gen_line_upd_bt(p.gl, p.lup, s, v.xg, sl.so, sl.sn, v.spec0, v.twM, p.pM, N, p.T, v.prm,
+                                                  first, br);
                 if (p.sml)
                     return admm::sm::launch_line_upd(M, N, planes, s, v.xg, sl.so, sl.sn, nullptr, v.spec0, v.twM, v.prm,
                                                      first);
@@ -1017,6 +1045,9 @@ int two_pass_reverse(const TwoPass& c, const SweepBufs& b, const float* x_bar, i
         const float* skk = b.xK ? r.skk : nullptr;   // s_k and D x_K enter rho_bar's <D vbar, D x_k> only
         if (!iso) {
             rc = ln.run(ADMM_K_ADJ, [&] {
+                if (c.bt)
+                    return launch_line_adj_bt(c.L, c.T, c.gl, alds, s, c.spec1, r.sk1, skk, b.xK, r.sbi, r.sbo, b.vsum,
+                                              c.spec0, r.rp, c.twM, c.N, c.prm, k == 1 ? 1 : 0, k == K ? 1 : 0, c.br);
                 return launch_line_adj(c.L, c.T, c.gl, alds, s, c.spec1, r.sk1, skk, b.xK, r.sbi, r.sbo, b.vsum, c.spec0,
                                        r.rp, c.twM, c.N, c.prm, k == 1 ? 1 : 0, k == K ? 1 : 0, ln_traj, c.br, c.pbs);
             });
@@ -1056,7 +1087,7 @@ int two_pass_reverse(const TwoPass& c, const SweepBufs& b, const float* x_bar, i
 // line adjoint look the plane's group up; the isotropic kernels read the one scalar block).
 int runtime_reverse(Launcher& ln, const GenPass& p, const FwdView& v, const SweepBufs& b, const float* x_bar,
                     const float* xK, int K, bool iso, int rows, int r_off, const admm_batch_reducer* red,
-                    const Branches& br = kOneSolve) {
+                    const Branches& br = kOneSolve, bool bt = false) {
     namespace g = admm::gen;
     hipStream_t s = ln.s;
     const int M = p.M, N = p.N;
@@ -1079,8 +1110,12 @@ int runtime_reverse(Launcher& ln, const GenPass& p, const FwdView& v, const Swee
         const RevStep r = rev_step(k, K, b, sstride, MN, rows);
         if (!iso) {
             rc = ln.run(ADMM_K_ADJ, [&] {
+                if (bt)   // ADMM_ISO_PLANE
+                    return launch_gen_line_adj_bt(p.gl, p.lup, s, vb, r.sk1, r.skk, xK, r.sbi, r.sbo, b.vsum, v.spec0, r.rp,
+                                                  v.twM, p.pM, N, p.T, v.prm, br);
                 hipLaunchKernelGGL(g::line_adj_kernel, p.gl, dim3(256), p.lup, s, vb, r.sk1, r.skk, xK, r.sbi, r.sbo,
                                    b.vsum, v.spec0, r.rp, v.twM, p.pM, N, p.T, v.prm, br);
+                return 0;
             });
             if (rc) return rc;
             continue;
@@ -1231,7 +1266,7 @@ int assemble_grads(Launcher& ln, const BwdView& v, const BwdLayout& bl, const Ca
     // (rho_bar, tau_bar): every row into one pair -- or, anisotropic grouped, per (lambda, rho) pair its planes' rows
     const Branches all{c.P * c.B, 0, c.P, 0u, 0u, 0, 0};   // one pair for every group: one segment of all planes
     int rc = ln.run(ADMM_K_FINAL, [&] {
-        if (!gr.on() || c.iso) launch_reduce_cols(s, b.part, v.rt, red_rows, 2, v.rtmp);
+        if (!gr.on() || iso_batch(c.iso)) launch_reduce_cols(s, b.part, v.rt, red_rows, 2, v.rtmp);
         else launch_reduce_groups(s, b.part, v.rt, c.maxit, (size_t)bl.nblk_line, bl.nblk_line / (int)planes, 2,
                                   gr.nparam > 1 ? gr.br : all, gr.nparam, gr.split_rt, gr.gtmp);
     });
@@ -1297,7 +1332,7 @@ int launch_backward(int phases, const Call& c, const Grads& g, const PathPlan& p
     hipStream_t s = reinterpret_cast<hipStream_t>(c.stream);
     Launcher ln{s, g_prof.on, {}};
     const int M = c.M, N = c.N, kh = c.kh, K = c.maxit;
-    const bool iso = c.iso != 0;
+    const bool iso = iso_batch(c.iso), bt = iso_plane(c.iso);
     const size_t planes = c.planes(), MN = (size_t)M * N;
     const Grouping gr = grouping_of(c, bl, ws);
     if (K == 0) {
@@ -1347,6 +1382,7 @@ int launch_backward(int phases, const Call& c, const Grads& g, const PathPlan& p
     auto grid = [&] {   // the 2-pass grid of the sweep and of y_bar = H Vsum (power-of-two shapes)
         TwoPass t = two_pass_single(ln, M, N, planes, bwd_line_T(M, N, iso), v.f, gr.br);
         t.rows = bl.nblk_line, t.r_off = bl.nblk_isoA;
+        t.bt = bt;
         return t;
     };
     switch (plan.bwd) {
@@ -1369,7 +1405,7 @@ int launch_backward(int phases, const Call& c, const Grads& g, const PathPlan& p
         }
         case ADMM_PATH_SWEEP_RUNTIME:
         case ADMM_PATH_SWEEP_RUNTIME_ISO:
-            rc = runtime_reverse(ln, gpass, v.f, b, g.x_bar, c.x_out, K, iso, bl.nblk_line, bl.nblk_isoA, c.red, gr.br);
+            rc = runtime_reverse(ln, gpass, v.f, b, g.x_bar, c.x_out, K, iso, bl.nblk_line, bl.nblk_isoA, c.red, gr.br, bt);
             break;
         default:
             rc = two_pass_reverse(grid(), b, g.x_bar, K, iso, plan.ln_traj, c.red);
@@ -1584,6 +1620,68 @@ int launch_forward_state(const Call& c, const StateLayout& L, int path) {
     }
     const int rc2 = ln.finish();
     return rc ? rc : rc2;
+}
+
+}  // namespace admm_capi
+
+// ---- the per-plane isotropic mode (ADMM_ISO_PLANE): its kernels and their instantiations, last of all ----
+#include "admm_plane_bt.hip"
+
+namespace admm_capi {
+
+int launch_line_bt(int L, int T, dim3 g, size_t lds, hipStream_t s, const float2* spec1, float2* spec0, const float* so,
+                   float* sn, const float2* twM, int N, const float* prm, int sz, int nt, const Branches& br) {
+    // every (L, T, threads) launch_line dispatches, single (GRP = false) and grouped
+#define X4(l, t, n, grp)                                                                                          \
+    if (L == l && T == t && nt == n && (br.nbr == 0) == grp) {                                                    \
+        set_lds(line_bt_kernel<l, t, n, grp>, lds);                                                               \
+        line_bt_kernel<l, t, n, grp><<<g, n, lds, s>>>(spec1, spec0, so, sn, nullptr, twM, N, prm, sz, br);       \
+        return 0;                                                                                                 \
+    }
+#define X3(l, t, n) X4(l, t, n, false) X4(l, t, n, true)
+#define X(l, t) X3(l, t, kThreads)
+    X3(256, 8, 512) X3(256, 16, 1024) X3(256, 4, 512) X3(256, 8, 1024)
+    ADMM_LT_CASES(X)
+#undef X
+#undef X3
+#undef X4
+    return -1;
+}
+
+int launch_line_adj_bt(int L, int T, dim3 g, size_t lds, hipStream_t s, const float2* spec1, const float* sk1,
+                       const float* sk, const float* xK, const float* sb_in, float* sb_out, float* vsum, float2* spec0,
+                       double* part, const float2* twM, int N, const float* prm, int first_k, int last_k,
+                       const Branches& br) {
+    if (br.nbr == 0) return -1;   // (the grouped adjoint has no per-plane isotropic form)
+#define X(l, t)                                                                                                    \
+    if (L == l && T == t) {                                                                                        \
+        set_lds(line_adj_bt_kernel<l, t>, lds);                                                                    \
+        line_adj_bt_kernel<l, t><<<g, kThreads, lds, s>>>(spec1, sk1, sk, xK, sb_in, sb_out, vsum, spec0, part,    \
+                                                           twM, N, prm, first_k, last_k, br);                      \
+        return 0;                                                                                                  \
+    }
+    ADMM_LT_CASES(X)
+#undef X
+    return -1;
+}
+
+int launch_gen_line_upd_bt(dim3 g, size_t lds, hipStream_t s, const float* x, const float* so, float* sn, float2* spec,
+                           const float2* twM, const admm::gen::FPlan& pM, int N, int T, const float* prm, int first,
+                           const Branches& br) {
+    set_lds(admm::gen::line_upd_bt_kernel, lds);
+    hipLaunchKernelGGL(admm::gen::line_upd_bt_kernel, g, dim3(256), lds, s, x, so, sn, (const float*)nullptr, spec, twM, pM,
+                       N, T, prm, first, br);
+    return 0;
+}
+
+int launch_gen_line_adj_bt(dim3 g, size_t lds, hipStream_t s, const float* vb, const float* sk1, const float* sk,
+                           const float* xK, const float* sb_in, float* sb_out, float* vsum, float2* spec, double* part,
+                           const float2* twM, const admm::gen::FPlan& pM, int N, int T, const float* prm,
+                           const Branches& br) {
+    set_lds(admm::gen::line_adj_bt_kernel, lds);
+    hipLaunchKernelGGL(admm::gen::line_adj_bt_kernel, g, dim3(256), lds, s, vb, sk1, sk, xK, sb_in, sb_out, vsum, spec, part,
+                       twM, pM, N, T, prm, br);
+    return 0;
 }
 
 }  // namespace admm_capi

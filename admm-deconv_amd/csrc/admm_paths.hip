@@ -103,8 +103,9 @@ bool enough_planes(const PathIn& q, MinPlanesFor which) {
 // streams 97-149 ms, profiles/r06_c4_mall_streams_sweep.txt -- their 4-5 plane chunks are too small: 4 x 4 97.0,
 // 5 x 4 85.3 ms; with 8 hardware queues 6 / 8 streams are slower still, profiles/r06_c4_hw_queues_probe.txt).
 // The smooth-length 2-pass kernels gain the same way (480 x 640 x 64 / 256 +5 / +7 %, 384^2 x 512 +11 %).
-ChunkPlan forward_chunks(int M, int N, size_t planes, bool iso, int fwd_path) {
+ChunkPlan forward_chunks(int M, int N, size_t planes, bool iso, int fwd_path, bool bt) {
     const size_t base = chunk_planes(planes, iso);
+    if (bt) return {base, 1};   // ADMM_ISO_PLANE: plain chunks, never the MALL schedule
     const int n = opt(ADMM_OPT_MALL_STREAMS);
     const bool two_pass = fwd_path == ADMM_PATH_2PASS || fwd_path == ADMM_PATH_SMOOTH || fwd_path == ADMM_PATH_RUNTIME;
     if (iso || n <= 1 || !two_pass) return {base, 1};
@@ -175,6 +176,18 @@ const FwdRule kFwdRules[] = {
 PathPlan plan_paths(const PathIn& q) {
     PathPlan pl;
     const bool rec = q.mode != ADMM_MODE_FORWARD;
+    if (q.bt) {
+        // ADMM_ISO_PLANE: the block-threshold line kernels exist on the 2-pass and the runtime-length grid only, and
+        // the path never depends on the plane count or the options (a plane's result does not depend on its batch);
+        // the recording is the natural-layout s_k (ADMM_REC_MASKS accepted, not honoured)
+        const bool gen = generic_shape(q.M, q.N);
+        pl.fwd = gen ? ADMM_PATH_RUNTIME : ADMM_PATH_2PASS;
+        if (rec) {
+            pl.want_h = (q.mode == ADMM_MODE_RECORD ? (q.rec_flags & ADMM_REC_HBAR) != 0 : q.h_bar) && q.psf;
+            pl.bwd = gen ? ADMM_PATH_SWEEP_RUNTIME : ADMM_PATH_SWEEP_2PASS;
+        }
+        return pl;
+    }
     if (rec) {
         pl.want_h = (q.mode == ADMM_MODE_RECORD ? (q.rec_flags & ADMM_REC_HBAR) != 0 : q.h_bar) && q.psf;
         // the fused kernel records s in its lane-native layout (no dim-2 spectra: not with h_bar)
@@ -207,8 +220,9 @@ PathPlan plan_paths(const PathIn& q) {
 // 256 x 256 anisotropic from the fused kernel's plane count on: plane256_kernel over per-group lane-native tables;
 // the other tuned shapes (and 256 x 256 below the rule, or isotropic): the 2-pass kernels; every other shape: the
 // runtime-length kernels.  The smooth-length, CU-resident and fused isotropic kernels take one table set only.
-int plan_grouped(int M, int N, bool iso, size_t planes) {
+int plan_grouped(int M, int N, bool iso, size_t planes, bool bt) {
     if (generic_shape(M, N)) return ADMM_PATH_RUNTIME;
+    if (bt) return ADMM_PATH_2PASS;   // ADMM_ISO_PLANE: never the fused kernel
     const PathIn q{M, N, iso, true, ADMM_MODE_FORWARD, 0, false, false, planes};
     if (fused_shape(M, N, iso) && fused_enabled() && enough_planes(q, kMinFused)) return ADMM_PATH_FUSED;
     return iso ? ADMM_PATH_2PASS_ISO : ADMM_PATH_2PASS;
@@ -301,7 +315,7 @@ int admm_query_paths(int M, int N, int iso, int kh, long long planes, int mode, 
     const int rc = check_shape(M, N, 1, 1, kh, kh, iso);
     if (rc) return rc;
     if (planes < 0) return fail(ADMM_E_INVALID, "admm_query_paths: planes must be >= 0");
-    const PathPlan pl = plan_paths({M, N, iso != 0, kh > 0, mode, flags, want_hbar != 0, want_rho != 0, (size_t)planes});
+    const PathPlan pl = plan_paths(path_in(M, N, iso, kh > 0, mode, flags, want_hbar != 0, want_rho != 0, (size_t)planes));
     *fwd_path = pl.fwd;
     *bwd_path = pl.bwd;
     return ADMM_OK;
@@ -313,8 +327,8 @@ int admm_query_forward_schedule(int M, int N, int iso, int kh, long long planes,
     const int rc = check_shape(M, N, 1, 1, kh, kh, iso);
     if (rc) return rc;
     if (planes <= 0) return fail(ADMM_E_INVALID, "admm_query_forward_schedule: planes must be > 0");
-    const PathPlan pl = plan_paths({M, N, iso != 0, kh > 0, ADMM_MODE_FORWARD, 0, false, false, (size_t)planes});
-    const ChunkPlan cp = forward_chunks(M, N, (size_t)planes, iso != 0, pl.fwd);
+    const PathPlan pl = plan_paths(path_in(M, N, iso, kh > 0, ADMM_MODE_FORWARD, 0, false, false, (size_t)planes));
+    const ChunkPlan cp = forward_chunks(M, N, (size_t)planes, iso_batch(iso), pl.fwd, iso_plane(iso));
     *chunk_planes = (long long)std::min(cp.chunk, (size_t)planes);
     *streams = cp.streams;
     return ADMM_OK;
@@ -326,7 +340,7 @@ int admm_query_grouped_path(int M, int N, int iso, int kh, long long planes, int
     if (rc) return rc;
     if (planes < 0 || groups < 1 || (planes > 0 && groups > planes))
         return fail(ADMM_E_INVALID, "admm_query_grouped_path: planes must be >= 0 and 1 <= groups <= planes");
-    *fwd_path = plan_grouped(M, N, iso != 0, (size_t)planes);
+    *fwd_path = plan_grouped(M, N, iso_batch(iso), (size_t)planes, iso_plane(iso));
     return ADMM_OK;
 }
 
@@ -341,10 +355,11 @@ int admm_query_grouped_paths(int M, int N, int iso, int kh, long long planes, in
     if (planes < 0 || groups < 1 || (planes > 0 && groups > planes))
         return fail(ADMM_E_INVALID, "admm_query_grouped_paths: planes must be >= 0 and 1 <= groups <= planes");
     if (mode == ADMM_MODE_FORWARD) {
-        *fwd_path = plan_grouped(M, N, iso != 0, (size_t)planes);
+        *fwd_path = plan_grouped(M, N, iso_batch(iso), (size_t)planes, iso_plane(iso));
         *bwd_path = 0;
         return ADMM_OK;
     }
+    if (no_plane_mode(iso, "the grouped adjoint")) return ADMM_E_UNSUPPORTED;
     const bool want_h = mode == ADMM_MODE_RECORD ? (flags & ADMM_REC_HBAR) != 0 : want_hbar != 0;
     const PathPlan pl = plan_grouped_adjoint(M, N, iso != 0, kh > 0, (size_t)planes, want_h);
     *fwd_path = pl.fwd;
@@ -358,6 +373,7 @@ int admm_query_state_path(int M, int N, int iso, int kh, long long planes, int* 
     if (rc) return rc;
     if (planes < 0 || planes > (long long)kChunkPlanes)
         return fail(ADMM_E_INVALID, "admm_query_state_path: planes must be 0 .. %zu", kChunkPlanes);
+    if (no_plane_mode(iso, "the state call")) return ADMM_E_UNSUPPORTED;
     *fwd_path = plan_state(M, N, iso != 0, (size_t)planes);
     return ADMM_OK;
 }

@@ -116,6 +116,15 @@ struct Launcher {
 
 int check_shape(int M, int N, int P, int B, int kh, int kw, int iso);
 
+// The prox of a call from its `iso` argument (ADMM_ISO_*): any non-zero value but ADMM_ISO_PLANE is the reference's
+// batch-coupled BT.  ADMM_ISO_PLANE (BT of each pixel's own 2-vector, admm_plane_bt.hip) couples nothing: layouts,
+// chunking and sequences are the anisotropic ones (every `bool iso` below is iso_batch), with the block-threshold
+// line kernels in place of the ST ones; it runs the 2-pass / runtime-length kernels only (plan_paths).
+inline bool iso_batch(int iso) { return iso != 0 && iso != ADMM_ISO_PLANE; }
+inline bool iso_plane(int iso) { return iso == ADMM_ISO_PLANE; }
+// entry points without a per-plane isotropic form
+int no_plane_mode(int iso, const char* who);
+
 // Planes per launch sequence.  The 2-pass kernels index planes by blockIdx.y (<= 65535), so a larger
 // anisotropic forward runs as consecutive chunks of this many planes through one chunk-sized workspace
 // (planes are independent, ops.jl:168-173).  A multiple of 256: every chunk but the last fills whole
@@ -133,12 +142,12 @@ struct ChunkPlan {
     size_t chunk;
     int streams;
 };
-ChunkPlan forward_chunks(int M, int N, size_t planes, bool iso, int fwd_path);
+ChunkPlan forward_chunks(int M, int N, size_t planes, bool iso, int fwd_path, bool bt = false);
 // the library's own streams on the current device (created once; non-blocking)
 hipStream_t lib_stream(int i);
 struct PathPlan;
 // forward workspace bytes (one chunk layout, or one per stream of the MALL-resident schedule)
-size_t forward_ws_bytes(int M, int N, size_t planes, int kh, bool iso, const PathPlan* pl = nullptr);
+size_t forward_ws_bytes(int M, int N, size_t planes, int kh, int iso, const PathPlan* pl = nullptr);
 
 // Trajectory recorded by the forward for the backward (all optional).
 struct Traj {
@@ -162,7 +171,12 @@ struct PathIn {
     int rec_flags;       // ADMM_REC_* (record)
     bool h_bar, rho_bar; // backward: gradients asked for
     size_t planes;       // P * B of the call (0: unknown, no plane-count rule)
+    bool bt = false;     // ADMM_ISO_PLANE (iso is then false): 2-pass / runtime-length forward and sweep only
 };
+// the plan query of a call's `iso` argument
+inline PathIn path_in(int M, int N, int iso, bool psf, int mode, int rec_flags, bool h_bar, bool rho_bar, size_t planes) {
+    return PathIn{M, N, iso_batch(iso), psf, mode, rec_flags, h_bar, rho_bar, planes, iso_plane(iso)};
+}
 enum MinPlanesFor { kMinFused, kMinFusedIso, kMinResident, kMinResidentIso };
 struct PathPlan {
     bool want_h = false;     // the forward records the dim-2 spectra h_bar needs (2-pass column pass)
@@ -279,7 +293,7 @@ struct Carver {
 // One path decision (admm_paths.hip): the fused kernel at 256 x 256 anisotropic from the plane-count rule, the
 // 2-pass kernels at the other tuned shapes, the runtime-length kernels elsewhere (never the smooth-length, resident
 // or fused isotropic kernels, never the MALL chunk schedule).
-int plan_grouped(int M, int N, bool iso, size_t planes);
+int plan_grouped(int M, int N, bool iso, size_t planes, bool bt = false);
 // floats (C) / float2 (G) between the groups' 2-pass tables
 inline unsigned group_tab_f(int M, int N) { return (unsigned)(align_up((size_t)(M / 2 + 1) * N * 4) / 4); }
 // Workspace: the single-PSF forward layout of the whole batch, and behind it G consecutive blocks of each table

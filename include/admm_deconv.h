@@ -45,6 +45,28 @@ enum {
     ADMM_E_REDUCER = -5       /* the caller's batch reducer (admm_batch_reducer) failed       */
 };
 
+/* The prox of a call: the `iso` argument of every entry point.  Any non-zero value other than ADMM_ISO_PLANE
+ * means ADMM_ISO_BATCH, as before this constant existed.
+ *   ADMM_ISO_NONE   anisotropic TV: soft-thresholding of every component of D x (ops.jl:9)
+ *   ADMM_ISO_BATCH  the reference's isotropic prox: block-thresholding with pixelnorm over both difference channels
+ *                   of EVERY plane of the call (ops.jl:6,10) -- the result of a plane depends on the rest of the batch
+ *   ADMM_ISO_PLANE  isotropic TV of each image plane on its own (the ROF definition, sum over pixels of
+ *                   sqrt(dx^2 + dy^2)): block-thresholding of each pixel's own 2-vector,
+ *                     n = sqrt(s1^2 + s2^2),  f = n > tau ? max(1 - tau / n, 0) : 0,  z = f s,  u = (1 - f) s,
+ *                   i.e. tvd_fft(..., isotropic = true) applied to every (M, N, 1, 1) plane alone, except that
+ *                   n = 0 gives f = 0 and never NaN (the reference yields NaN at tau = 0, n = 0).
+ *                   Planes are independent: no plane limit on the forward (chunks of 65,280 planes as for
+ *                   ADMM_ISO_NONE), the reducer is ignored, a grouped call may carry nparam = G scalar pairs, the
+ *                   workspace is the anisotropic layout.  Paths: ADMM_PATH_2PASS at every tuned power-of-two shape
+ *                   (256 x 256 included, whatever the plane count), ADMM_PATH_RUNTIME elsewhere; the sweeps
+ *                   ADMM_PATH_SWEEP_2PASS / _RUNTIME; never the fused, smooth-length, CU-resident or MALL-stream
+ *                   paths; ADMM_REC_MASKS is accepted and not honoured.  ADMM_E_UNSUPPORTED: the state calls, the
+ *                   grouped record / backward entries (the multi-branch entries are flag-driven and have no flag). */
+enum { ADMM_ISO_NONE = 0, ADMM_ISO_BATCH = 1, ADMM_ISO_PLANE = 2 };
+
+/* 1: this build knows ADMM_ISO_PLANE (an older library has no such symbol and reads iso = 2 as ADMM_ISO_BATCH). */
+int admm_iso_plane_supported(void);
+
 /* Kernel classes, for the optional per-kernel profiler (admm_profile_*). */
 enum {
     ADMM_K_SETUP = 0,   /* twiddles + C spectrum (ops.jl:22-37)                                 */
@@ -72,9 +94,10 @@ int admm_tvd_workspace_bytes(int M, int N, int P, int B, int kh, int kw, int iso
 /* The solve.  Replaces tvd_fft(y, λ, ρ, h, isotropic, maxit) (ops.jl:181-188) for device
  * arrays: returns x after `maxit` ADMM iterations of
  *   x = irfft(C .* rfft(H^T y + ρ D^T(z-u))),  z = prox(Dx+u, λ/ρ),  u = u + Dx - z
- * with prox = ST (iso == 0, ops.jl:9) or BT (iso == 1, ops.jl:10; couples the whole batch).
+ * with prox = ST (iso == 0, ops.jl:9), BT (iso == 1, ops.jl:10; couples the whole batch) or BT per plane
+ * (iso == ADMM_ISO_PLANE, above).
  * maxit == 0 returns zeros (the reference's initial x, ops.jl:46).
- * Batch size: iso == 1 takes at most 65535 planes (P*B) per call.  iso == 0 takes any number; above
+ * Batch size: iso == 1 takes at most 65535 planes (P*B) per call.  iso == 0 and 2 take any number; above
  * 65,280 planes the library solves consecutive chunks of 65,280 planes through one chunk-sized
  * workspace (admm_tvd_workspace_bytes sizes it).  The adjoint entry points below take at most 65535
  * planes per call. */
@@ -245,7 +268,8 @@ int admm_tvd_backward_multi_recorded_dev_f32(const float* x_bar, float* y_bar, f
  * the single-PSF call through the same kernels.  iso = 1: the reference's batch coupling is kept: the pixel norm
  * sums over ALL planes of the call, whatever their group (ops.jl:6), while each plane's x-update uses its own group's
  * C and H^T y; the BT factor is one map per batch, so an isotropic call takes nparam = 1 (nparam = G > 1:
- * ADMM_E_UNSUPPORTED).  There is no sharded (reducer) form.
+ * ADMM_E_UNSUPPORTED).  iso = ADMM_ISO_PLANE: as iso = 0, every plane alone with its group's h, lambda and rho
+ * (nparam = G allowed), never the fused kernel.  There is no sharded (reducer) form.
  * Limits: shapes as admm_tvd_forward_f32 (2..4096 per side, kh <= M, kw <= N); at most 65,280 planes per call (no
  * internal chunking); maxit = 0 returns zeros.  ADMM_E_INVALID: gb not in {1, B}, gp not in {1, P}, nparam not in
  * {1, G}, NULL lambda / rho, NULL h with kh > 0.  Asynchronous on `stream`, allocates nothing, deterministic, never
@@ -273,7 +297,7 @@ int admm_query_grouped_path(int M, int N, int iso, int kh, long long planes, int
  * h_bar `float[G][kw][kh]`, one gradient per group's PSF; lambda_bar, rho_bar: nparam floats each -- nparam = G:
  * entry g sums over group g's planes, nparam = 1: the entry sums over all planes.  iso = 1 keeps the forward's batch
  * coupling (R maps and the norm over all planes, whatever their group); nparam is then 1 (nparam = G > 1:
- * ADMM_E_UNSUPPORTED) and h_bar is still per group.
+ * ADMM_E_UNSUPPORTED) and h_bar is still per group.  iso = ADMM_ISO_PLANE: ADMM_E_UNSUPPORTED (no grouped adjoint yet).
  * The record / replay pair follows the single one's contract: rec_flags takes ADMM_REC_HBAR (record the extra
  * trajectory h_bar needs; the replay must then be given h_bar, and only then); ADMM_REC_MASKS is accepted and not
  * honoured (the full trajectory is recorded and rho_bar stays available).  The replay differentiates the recorded

@@ -58,12 +58,16 @@ _psf(h) = isempty(h) ? nothing : (h isa ROCArray{Float32} ? h : ROCArray(Float32
 const _FwdSig = (Ptr{Float32}, Ptr{Float32}, Cint, Cint, Cint, Cint, Ptr{Float32}, Cint, Cint,
                  Ptr{Float32}, Ptr{Float32}, Cint, Cint, Ptr{Cvoid}, Csize_t, Ptr{Cvoid}, Ptr{Cvoid})
 
+# The C ABI's `iso` argument (include/admm_deconv.h, ADMM_ISO_*): `isotropic::Bool` below maps to 0 / 1.
+const ADMM_ISO_PLANE = Cint(2)
+
 """
     tvd_fft(y::ROCArray{Float32,4}, λ, ρ=[1f0], h=ROCArray{Float32}(undef,0), isotropic=false, maxit=100)
 
 Drop-in for `tvd_fft` (src/ops/ops.jl:181) on MI355X: same arguments, same (M,N,P,B) layout,
 returns a new array.  λ and ρ are 1-element arrays (or scalars), already clamped by the layer; as
 device arrays they are read in-kernel (admm_tvd_forward_dev_f32), so the call never syncs the host.
+The library also solves isotropic TV per image plane (`iso = ADMM_ISO_PLANE`); this shim does not pass it yet.
 """
 function tvd_fft(y::ROCArray{Float32, 4}, λ, ρ = Float32[1], h = ROCArray{Float32}(undef, 0),
                  isotropic::Bool = false, maxit::Integer = 100)
