@@ -100,6 +100,74 @@ __global__ __launch_bounds__(512) void pair_bench_kernel(const float* __restrict
     for (int n = 0; n < 64; ++n) o[2 * n] = S[n];
 }
 
+// line_inverse_pair_staged: registers 32..63 of the result come back from the per-lane LDS staging slots
+__global__ __launch_bounds__(512) void pair_inv_staged_kernel(const float2* __restrict__ spec, float* __restrict__ x) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char stage_raw[];
+    float2* stg = reinterpret_cast<float2*>(stage_raw) + threadIdx.x;
+    const int r = blockIdx.x * 256 + (threadIdx.x >> 1);
+    const bool hb = threadIdx.x & 1;
+    const float2* in = spec + (size_t)r * 128 + (hb ? 64 : 0);
+    float2 S[64];
+#pragma unroll
+    for (int m = 0; m < 64; ++m) S[m] = in[m];
+    admm::line_inverse_pair_staged(S, hb, stg, stg + 16 * 512);
+#pragma unroll
+    for (int m = 0; m < 32; ++m) S[32 + m] = stg[m * 512];
+    float2* row = reinterpret_cast<float2*>(x + (size_t)r * 256) + (hb ? 1 : 0);
+#pragma unroll
+    for (int n = 0; n < 64; ++n) row[2 * n] = S[n];
+}
+
+// The complex primitives, constant twiddles and butterflies of fft_reg.hpp / line_pair.hpp on 16 values per thread
+// (in[j * 64 + t]), every result to its own slot (out[slot * 64 + t]): the packed build of this file against its
+// scalar twin, bit for bit (tests/test_gpu_packed.py).  One block of 64 threads.
+constexpr int kPrimIn = 16;
+struct PrimOut {
+    float2* out;
+    int slot;
+    __device__ void put(float2 v) { out[(slot++) * 64 + threadIdx.x] = v; }
+};
+template <bool INV, int... E>
+__device__ void prim_w16(PrimOut& o, float2 v) { (o.put(admm::w16<E, INV>(v)), ...); }
+template <bool INV, int... E>
+__device__ void prim_w256(PrimOut& o, float2 v) { (o.put(admm::w256<E, INV>(v)), ...); }
+template <int R, bool INV>
+__device__ void prim_dft(PrimOut& o, const float2 (&a)[kPrimIn]) {
+    float2 v[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) v[r] = a[r];
+    admm::dft<R, INV>(v);
+#pragma unroll
+    for (int r = 0; r < R; ++r) o.put(v[r]);
+}
+template <bool INV>
+__device__ void prim_dir(PrimOut& o, const float2 (&a)[kPrimIn]) {
+    o.put(admm::rot<INV>(a[0]));
+    prim_w16<INV, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15>(o, a[2]);
+    prim_w256<INV, 0, 64, 128, 192, 1, 2, 3, 17, 32, 63, 65, 96, 101, 127, 129, 160, 191, 193, 224, 255>(o, a[3]);
+    prim_dft<2, INV>(o, a);
+    prim_dft<4, INV>(o, a);
+    prim_dft<8, INV>(o, a);
+    prim_dft<16, INV>(o, a);
+}
+__global__ __launch_bounds__(64) void prims_kernel(const float2* __restrict__ in, float2* __restrict__ out, int* nslots) {
+    float2 a[kPrimIn];
+#pragma unroll
+    for (int j = 0; j < kPrimIn; ++j) a[j] = in[j * 64 + threadIdx.x];
+    PrimOut o{out, 0};
+    o.put(admm::cadd(a[0], a[1]));
+    o.put(admm::csub(a[0], a[1]));
+    o.put(admm::cmul(a[0], a[1]));
+    o.put(admm::cscale(a[0], a[1].x));
+    o.put(admm::cconj(a[0]));
+    o.put(admm::cadd(a[2], admm::cconj(a[3])));
+    o.put(admm::csub(a[2], admm::rot<false>(a[3])));
+    prim_dir<false>(o, a);
+    prim_dir<true>(o, a);
+    if (threadIdx.x == 0) *nslots = o.slot;
+}
+constexpr int kPrimSlots = 7 + 2 * (1 + 16 + 20 + 2 + 4 + 8 + 16);
+
 }  // namespace
 
 template <int MODE, bool PSF = false>
@@ -207,6 +275,26 @@ int devtest_line_bench(const float* x, float* y, int rows, int reps, int quad, f
     hipEventDestroy(a);
     hipEventDestroy(b);
     return ok ? 0 : -4;
+}
+int devtest_pair_inverse_staged(const float* spec, float* x, int rows) {
+    const int lds = 32 * 512 * 8;
+    (void)hipFuncSetAttribute((const void*)pair_inv_staged_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    pair_inv_staged_kernel<<<rows / 256, 512, lds>>>(reinterpret_cast<const float2*>(spec), x);
+    return hipDeviceSynchronize() == hipSuccess ? 0 : -4;
+}
+// in: 16 x 64 float2, out: devtest_prims_slots() x 64 float2 (device pointers); nslots: one device int, the slots written
+int devtest_prims_slots() { return kPrimSlots; }
+int devtest_prims(const float* in, float* out, int* nslots) {
+    prims_kernel<<<1, 64>>>(reinterpret_cast<const float2*>(in), reinterpret_cast<float2*>(out), nslots);
+    return hipDeviceSynchronize() == hipSuccess ? 0 : -4;
+}
+// 1 when this library was built with the packed-FP32 forms (ADMM_PK_F32), 0 for the scalar twin
+int devtest_packed() {
+#ifdef ADMM_PK_F32
+    return 1;
+#else
+    return 0;
+#endif
 }
 int devtest_pair_inverse(const float* spec, float* x, int rows) {
     pair_inv_kernel<<<rows / 256, 512>>>(reinterpret_cast<const float2*>(spec), x);

@@ -15,15 +15,28 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#ifdef ADMM_PK_F32
+#include "fft_pk.hpp"
+#endif
+
 namespace admm {
 
+#ifdef ADMM_PK_F32
+__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return pk(vec(a) + vec(b)); }
+__device__ __forceinline__ float2 csub(float2 a, float2 b) { return pk(vec(a) - vec(b)); }
+#else
 __device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
 __device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
+#endif
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) {
     return make_float2(fmaf(a.x, b.x, -a.y * b.y), fmaf(a.x, b.y, a.y * b.x));
 }
 __device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y); }
+#ifdef ADMM_PK_F32
+__device__ __forceinline__ float2 cscale(float2 a, float s) { return pk(vec(a) * s); }
+#else
 __device__ __forceinline__ float2 cscale(float2 a, float s) { return make_float2(a.x * s, a.y * s); }
+#endif
 // multiply by -i (forward) or +i (inverse)
 template <bool INV>
 __device__ __forceinline__ float2 rot(float2 a) {
@@ -43,6 +56,14 @@ constexpr float kS16[16] = {0.0f, 0.382683432365089772f, 0.707106781186547524f, 
                             -1.0f, -0.923879532511286756f, -0.707106781186547524f, -0.382683432365089772f};
 
 // v * W16^E (forward, W16 = exp(-2 pi i/16)) or v * conj(W16^E) (inverse)
+#ifdef ADMM_PK_F32
+template <int E, bool INV>
+__device__ __forceinline__ f2v vw16(f2v v);
+template <int R, bool INV>
+__device__ __forceinline__ void vdft(f2v (&v)[R]);
+template <int E, bool INV>
+__device__ __forceinline__ float2 w16(float2 v) { return pk(vw16<E, INV>(vec(v))); }
+#else
 template <int E, bool INV>
 __device__ __forceinline__ float2 w16(float2 v) {
     constexpr int e = E & 15;
@@ -60,6 +81,7 @@ __device__ __forceinline__ float2 w16(float2 v) {
         return make_float2(fmaf(v.x, c, -v.y * s), fmaf(v.x, s, v.y * c));
     }
 }
+#endif
 
 template <bool INV>
 __device__ __forceinline__ void dft2(float2& a, float2& b) {
@@ -68,6 +90,14 @@ __device__ __forceinline__ void dft2(float2& a, float2& b) {
     b = csub(t, b);
 }
 
+#ifdef ADMM_PK_F32
+template <bool INV>
+__device__ __forceinline__ void dft4(float2& v0, float2& v1, float2& v2, float2& v3) {
+    f2v a = vec(v0), b = vec(v1), c = vec(v2), d = vec(v3);
+    vdft4<INV>(a, b, c, d);
+    v0 = pk(a); v1 = pk(b); v2 = pk(c); v3 = pk(d);
+}
+#else
 template <bool INV>
 __device__ __forceinline__ void dft4(float2& v0, float2& v1, float2& v2, float2& v3) {
     const float2 s02 = cadd(v0, v2), d02 = csub(v0, v2);
@@ -77,7 +107,19 @@ __device__ __forceinline__ void dft4(float2& v0, float2& v1, float2& v2, float2&
     v1 = cadd(d02, d13);
     v3 = csub(d02, d13);
 }
+#endif
 
+#ifdef ADMM_PK_F32
+template <int R, bool INV>
+__device__ __forceinline__ void dft(float2 (&v)[R]) {
+    f2v w[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) w[r] = vec(v[r]);
+    vdft<R, INV>(w);
+#pragma unroll
+    for (int r = 0; r < R; ++r) v[r] = pk(w[r]);
+}
+#else
 template <int R, bool INV>
 __device__ __forceinline__ void dft(float2 (&v)[R]) {
     if constexpr (R == 1) {
@@ -119,6 +161,75 @@ __device__ __forceinline__ void dft(float2 (&v)[R]) {
         }
     }
 }
+#endif
+
+#ifdef ADMM_PK_F32
+// ---- packed forms of w16 / dft (fft_pk.hpp), op for op the scalar ones above ----------------------------------
+template <int E, bool INV>
+__device__ __forceinline__ f2v vw16(f2v v) {
+    constexpr int e = E & 15;
+    if constexpr (e == 0) {
+        return v;
+    } else if constexpr (e == 4) {
+        return vrot<INV>(v);
+    } else if constexpr (e == 8) {
+        return -v;
+    } else if constexpr (e == 12) {
+        return vrot<!INV>(v);
+    } else {
+        constexpr float c = kC16[e];
+        constexpr float s = INV ? kS16[e] : -kS16[e];
+        return vmulc_reg(v, c, s);
+    }
+}
+
+template <int R, bool INV>
+__device__ __forceinline__ void vdft(f2v (&v)[R]) {
+    if constexpr (R == 1) {
+    } else if constexpr (R == 2) {
+        const f2v t = v[0];
+        v[0] = t + v[1];
+        v[1] = t - v[1];
+    } else if constexpr (R == 4) {
+        vdft4<INV>(v[0], v[1], v[2], v[3]);
+    } else if constexpr (R == 8) {
+        f2v a0 = v[0] + v[4], a1 = v[1] + v[5], a2 = v[2] + v[6], a3 = v[3] + v[7];
+        f2v b0 = v[0] - v[4], b1 = v[1] - v[5], b2 = v[2] - v[6], b3 = v[3] - v[7];
+        b1 = vw16<2, INV>(b1);
+        b2 = vw16<4, INV>(b2);
+        b3 = vw16<6, INV>(b3);
+        vdft4<INV>(a0, a1, a2, a3);
+        vdft4<INV>(b0, b1, b2, b3);
+        v[0] = a0; v[2] = a1; v[4] = a2; v[6] = a3;
+        v[1] = b0; v[3] = b1; v[5] = b2; v[7] = b3;
+    } else {
+        f2v a[4][4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            a[q][0] = v[q]; a[q][1] = v[q + 4]; a[q][2] = v[q + 8]; a[q][3] = v[q + 12];
+            vdft4<INV>(a[q][0], a[q][1], a[q][2], a[q][3]);
+        }
+        a[1][1] = vw16<1, INV>(a[1][1]);
+        a[1][2] = vw16<2, INV>(a[1][2]);
+        a[1][3] = vw16<3, INV>(a[1][3]);
+        a[2][1] = vw16<2, INV>(a[2][1]);
+        a[2][2] = vw16<4, INV>(a[2][2]);
+        a[2][3] = vw16<6, INV>(a[2][3]);
+        a[3][1] = vw16<3, INV>(a[3][1]);
+        a[3][2] = vw16<6, INV>(a[3][2]);
+        a[3][3] = vw16<9, INV>(a[3][3]);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            vdft4<INV>(a[0][m], a[1][m], a[2][m], a[3][m]);
+            v[m] = a[0][m]; v[m + 4] = a[1][m]; v[m + 8] = a[2][m]; v[m + 12] = a[3][m];
+        }
+    }
+}
+template <bool INV>
+__device__ __forceinline__ void dft4(f2v& v0, f2v& v1, f2v& v2, f2v& v3) { vdft4<INV>(v0, v1, v2, v3); }
+template <int R, bool INV>
+__device__ __forceinline__ void dft(f2v (&v)[R]) { vdft<R, INV>(v); }
+#endif
 
 // ---- radix plans: LEN = R0 * R1 * R2 (pass p runs with Ns = R0*...*R(p-1)) -------------------
 template <int LEN>

@@ -32,6 +32,14 @@ import subprocess
 INSN = re.compile(r"^\s+([a-z][a-z0-9_]*)(\s+(.*))?$")
 VREG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
 WIDE_STORE = re.compile(r"^(buffer|global|scratch|flat)_store_(dwordx3|dwordx4|b96|b128)$")
+# Translation units built with the packed-FP32 forms (-DADMM_PK_F32, csrc/fft_pk.hpp) get the same wait states after
+# the stores of a register PAIR as well: 64-bit VMEM stores and 64- / 128-bit LDS writes.  There a v_pk_*_f32 writes
+# the whole pair right behind the store that still reads it (the staged FFT outputs, the rows -> LDS copies, the
+# H^T y stores); with only the wide VMEM stores padded the packed PSF kernel failed the full-batch census (32-59 bad
+# planes of 512 per launch, varying run to run, also with 4 wait states on the wide stores), and passes it with
+# these padded (DESIGN.md s5 "Packed FP32").  Which of the two store kinds it is was not separated.
+PAIR_STORE = re.compile(r"^((buffer|global|scratch|flat)_store_(dwordx2|b64)|ds_write_b64|ds_write_b96|ds_write_b128|"
+                        r"ds_write2_b64|ds_write2st64_b64)$")
 # control transfers: the window cannot follow the jump into its target block, so it is closed (padded)
 # before the branch instead -- every path into a block then arrives with the wait states already spent
 BRANCH = re.compile(r"^s_(branch|cbranch_\w+|setpc_b64|swappc_b64|callpc_b64|call_b64)$")
@@ -53,6 +61,8 @@ def _store_data(mn, ops):
     parts = ops.split(",")
     if mn.startswith("buffer_"):
         return _vregs(parts[0])
+    if mn.startswith("ds_"):          # address, data [, second data of the write2 forms]
+        return _vregs(",".join(parts[1:3]))
     return _vregs(parts[1]) if len(parts) > 1 else set()
 
 
@@ -78,8 +88,8 @@ def _short(recent, dst=None):
     return short
 
 
-def pad_asm(text):
-    """Returns (padded assembly, number of s_nop inserted)."""
+def pad_asm(text, pairs=False):
+    """Returns (padded assembly, number of s_nop inserted).  pairs: also pad the register-pair stores (PAIR_STORE)."""
     out = []
     recent = []         # (data VGPRs of a wide store or empty, wait states of the instruction)
     inserted = 0
@@ -108,7 +118,8 @@ def pad_asm(text):
                 w = int(ops.split()[0]) + 1
             except (IndexError, ValueError):
                 w = 1
-        recent.append((_store_data(mn, ops) if WIDE_STORE.match(mn) else set(), w))
+        is_store = WIDE_STORE.match(mn) or (pairs and PAIR_STORE.match(mn))
+        recent.append((_store_data(mn, ops) if is_store else set(), w))
         if len(recent) > 8:
             recent = recent[-8:]
         out.append(line)
@@ -135,7 +146,8 @@ def scratch_sizes(text):
 
 def compile_tu(src, obj, flags, verbose=False, scratch_out=None):
     """hipcc -c `src` -> `obj` with `flags`, the device assembly padded by pad_asm.  Returns the s_nop count;
-    `scratch_out` (a dict), when given, receives every kernel's scratch bytes per lane (scratch_sizes)."""
+    `scratch_out` (a dict), when given, receives every kernel's scratch bytes per lane (scratch_sizes).  A TU compiled
+    with -DADMM_PK_F32 gets the register-pair stores padded as well (PAIR_STORE)."""
     work = obj + ".hz"
     shutil.rmtree(work, ignore_errors=True)
     os.makedirs(work)
@@ -145,12 +157,12 @@ def compile_tu(src, obj, flags, verbose=False, scratch_out=None):
     if r.returncode != 0 or not steps:
         raise RuntimeError(f"hipcc -### failed for {src}:\n{r.stderr[-2000:]}")
     try:
-        return _run_steps(steps, work, src, verbose, scratch_out)
+        return _run_steps(steps, work, src, verbose, scratch_out, "-DADMM_PK_F32" in flags)
     finally:
         shutil.rmtree(work, ignore_errors=True)   # also after a failed step (no .hipi left in the tree)
 
 
-def _run_steps(steps, work, src, verbose, scratch_out):
+def _run_steps(steps, work, src, verbose, scratch_out, pairs=False):
     total = 0
     for i, step in enumerate(steps):
         is_dev_as = "-cc1as" in step and "amdgcn-amd-amdhsa" in step
@@ -159,7 +171,7 @@ def _run_steps(steps, work, src, verbose, scratch_out):
             if not m:
                 raise RuntimeError(f"cannot find the device assembly in: {step[:200]}")
             path = os.path.join(work, m.group(1))
-            text, n = pad_asm(open(path).read())
+            text, n = pad_asm(open(path).read(), pairs)
             if scratch_out is not None:
                 scratch_out.update(scratch_sizes(text))
             open(path, "w").write(text)

@@ -1,10 +1,12 @@
 // plane_api.hpp -- host interface of the fused per-plane kernel (plane_launch.hip).
 //
-// The fused kernel lives in its own translation unit because it is compiled WITHOUT packed-FP32
-// VALU ops (-Xclang -target-feature -Xclang -packed-fp32-ops): with ROCm 7.2's gfx950 codegen the
-// register-dense code of this kernel produced nondeterministic lane corruption in v_pk_*_f32 results
-// (lanes 10-15 of a 16-lane group, found with a per-phase state dump).  Without
-// packed FP32 the kernel is bitwise deterministic.
+// The fused kernels live in their own translation units because of their flags: -fno-slp-vectorize and
+// -DADMM_PK_F32.  Their register transforms use the hand-written packed-FP32 forms of fft_pk.hpp (v_pk_add_f32 /
+// v_pk_mul_f32 / v_pk_fma_f32 on complex values held in aligned register pairs), bitwise the scalar forms every
+// other translation unit keeps.  The SLP vectorizer is off because, left on, it packs whatever scalar arithmetic it
+// finds and these register-dense kernels then spill (250-540 B of scratch per lane).  (Until the packed forms the
+// TUs were built with the packed-FP32 feature off altogether; the lane corruption that first prompted that was the
+// store-data hazard that hazard_pad.py pads)
 #pragma once
 #include <hip/hip_runtime.h>
 

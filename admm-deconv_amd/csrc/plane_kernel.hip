@@ -208,8 +208,14 @@ __device__ __forceinline__ void column_half(float2 (&S)[64], float2* colbuf, con
     sched_fence();
     // MODE 1 (H^T y, once per solve) loads its complex multipliers in two halves of 16: all 32 at once (64 VGPRs)
     // set the PSF kernel's register peak and its allocation spilled inside the iteration loop as well
+#ifdef ADMM_PK_F32
+    // packed build: the real multipliers too (their 32 VGPRs sit on the dft<8> peak, whose packed temporaries need
+    // aligned pairs: the reverse sweep's column phase went from 220 to 252 live VGPRs and spilled)
+    constexpr int NGF = 16;
+#else
     constexpr int NGF = MODE == 1 ? 16 : 32;
-    float cf[MODE == 0 ? 32 : 1];
+#endif
+    float cf[MODE == 0 ? NGF : 1];
     float2 gf[MODE == 1 ? 32 : 1];
 #pragma unroll
     for (int j = 0; j < NGF; ++j) {
@@ -246,16 +252,19 @@ __device__ __forceinline__ void column_half(float2 (&S)[64], float2* colbuf, con
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        if constexpr (MODE == 1 && NGF == 16) {
-            if (i == 2) {   // second half of the complex multipliers, into the slots of the first
+        if constexpr (NGF == 16) {
+            if (i == 2) {   // second half of the multipliers, into the slots of the first
                 sched_fence();
 #pragma unroll
-                for (int j = 0; j < 16; ++j) gf[j] = bld2(Gf, t * 8, (HALF * 32 + 16 + j) * kPT * 8);
+                for (int j = 0; j < 16; ++j) {
+                    if constexpr (MODE == 0) cf[j] = bld1(Cf, t * 4, (HALF * 32 + 16 + j) * kPT * 4);
+                    else gf[j] = bld2(Gf, t * 8, (HALF * 32 + 16 + j) * kPT * 8);
+                }
             }
         }
 #pragma unroll
         for (int q2 = 0; q2 < 8; ++q2) {
-            if constexpr (MODE == 0) u[i][q2] = cscale(u[i][q2], cf[i * 8 + q2]);
+            if constexpr (MODE == 0) u[i][q2] = cscale(u[i][q2], cf[(i * 8 + q2) % NGF]);
             else u[i][q2] = cmul(u[i][q2], gf[(i * 8 + q2) % NGF]);
         }
     }
@@ -658,7 +667,15 @@ __global__ __launch_bounds__(kPT) void plane256_kernel(const float* __restrict__
         line_forward_pair(S, hb);
         dbg_dump<DBG>(dbg, S, 4 * k, t);
     }
-    float2* xrow = reinterpret_cast<float2*>(x_out + bo.out_plane * 65536 + (size_t)r * 256);
+#ifdef ADMM_PK_F32
+    // the output row from a thread index taken here: formed from r, its address is computed at the kernel's start and
+    // held in a VGPR pair through every phase (the packed build has none to spare: 8 B of scratch per lane)
+    int ro = threadIdx.x >> 1;
+    __asm__ volatile("" : "+v"(ro));
+#else
+    const int ro = r;
+#endif
+    float2* xrow = reinterpret_cast<float2*>(x_out + bo.out_plane * 65536 + (size_t)ro * 256);
 #pragma unroll
     for (int n = 0; n < 64; ++n) xrow[2 * n + hb] = S[n];
     if constexpr (DBG >= 2) {

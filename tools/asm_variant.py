@@ -319,7 +319,9 @@ def run(cmd_line, cwd):
 
 def prepare(nopk, extra=""):
     os.makedirs(WORK, exist_ok=True)
-    flags = ("-Xclang -target-feature -Xclang -packed-fp32-ops " if nopk else "") + extra
+    # nopk: the scalar forms with the packed-FP32 feature off (the build before csrc/fft_pk.hpp); otherwise the
+    # product's flags, the hand-written packed forms without the SLP vectorizer (__graft_entry__.PK_F32)
+    flags = ("-Xclang -target-feature -Xclang -packed-fp32-ops " if nopk else "-fno-slp-vectorize -DADMM_PK_F32 ") + extra
     cmd = (f"hipcc -### --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c {flags} -mllvm -pragma-unroll-threshold=100000 "
            f"-save-temps -o plane_launch.o {CSRC}/plane_launch.hip")
     r = subprocess.run(cmd, shell=True, cwd=WORK, capture_output=True, text=True)

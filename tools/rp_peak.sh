@@ -1,7 +1,8 @@
 #!/bin/bash
 # Pre-register-allocation VGPR pressure of one resident-kernel shape (llc's amdgpu-print-rp on the MIR after
 # the machine scheduler): tools/rp_peak.sh SRC.hip "X(250,250)" [extra hipcc flags...].  Prints the peak and
-# the live-in registers of the peak block by defining opcode.  Measurement tool only.
+# the live-in registers of the peak block by defining opcode.  Measurement tool only.  (The resident kernels keep the
+# packed-FP32 feature off, as here; for a fused-plane TU replace the feature flags by -fno-slp-vectorize -DADMM_PK_F32.)
 set -e
 SRC=$1; SH=$2; shift 2
 L=/opt/rocm/lib/llvm/bin
