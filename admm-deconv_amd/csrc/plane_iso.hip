@@ -141,13 +141,13 @@ __device__ __forceinline__ void row_iso_b(float2 (&S)[64], rsrc_t sld, rsrc_t fl
         if (n == 0) {
             w2x0 = wv.z;
         } else {
-            S[n - 1] = finalize(wc[(n - 1) & 1], wv, hc[(n - 1) & 1], hb, bot, rho);
+            S[n - 1] = finalize(wc[(n - 1) & 1], wv, hc[(n - 1) & 1], hb, rho);
         }
         wc[n & 1] = wv;
         hc[n & 1] = hr[n % NR];
         sched_fence();
     }
-    S[63] = finalize(wc[1], make_float4(0.f, 0.f, w2x0, 0.f), hc[1], hb, bot, rho);
+    S[63] = finalize(wc[1], make_float4(0.f, 0.f, w2x0, 0.f), hc[1], hb, rho);
     lds_barrier();
     if (bot) {
         const float2* wbn = wb + (((w + 1) & 7) * 2 + hb) * 64;   // next wave's first line
@@ -467,12 +467,12 @@ __device__ __forceinline__ void row_isoadj_b(float2 (&S)[64], rsrc_t s1p, rsrc_t
         if (n == 0) {
             w2x0 = nb.z;
         } else {
-            S[n - 1] = finalize(wc[(n - 1) & 1], nb, zero2, hb, bot, 1.0f);
+            S[n - 1] = finalize(wc[(n - 1) & 1], nb, zero2, hb, 1.0f);
         }
         wc[n & 1] = nb;
         sched_fence();
     }
-    S[63] = finalize(wc[1], make_float4(0.f, 0.f, w2x0, 0.f), zero2, hb, bot, 1.0f);
+    S[63] = finalize(wc[1], make_float4(0.f, 0.f, w2x0, 0.f), zero2, hb, 1.0f);
 #pragma unroll
     for (int m = 0; m < 16; ++m) S[m] = stg[m * kPT];
 #pragma unroll

@@ -330,10 +330,11 @@ __device__ __forceinline__ float lane_down2(float& vr) {   // lane i <- lane i +
 
 // v(register n) = H^T y + rho D^T w, with w of registers n and n+1 (the partner lane's pixel after this
 // lane's last pixel lives one register later on lane A).
-__device__ __forceinline__ float2 finalize(float4 wn, float4 wnext, float2 hy, bool hb, bool bot, float rho) {
+// The wave's last line (lanes 62, 63) has no source lane in the two shifts: lane_down2 leaves +0 there (bound_ctrl), which
+// is what the sum needs until the next wave's first line is fixed up after the barrier -- no select on the lane.
+__device__ __forceinline__ float2 finalize(float4 wn, float4 wnext, float2 hy, bool hb, float rho) {
     const float recv = swapf(hb ? wn.z : wnext.z);     // w2 at the pixel after this lane's 2nd pixel
-    float w1x = lane_down2(wn.x), w1y = lane_down2(wn.y);   // w1 of line r+1
-    if (bot) w1x = w1y = 0.0f;                         // next wave's first line: fixed up after the barrier
+    const float w1x = lane_down2(wn.x), w1y = lane_down2(wn.y);   // w1 of line r+1; 0 on the wave's last line
     const float q0 = wn.x - w1x + wn.z - wn.w;
     const float q1 = wn.y - w1y + wn.w - recv;
     return make_float2(fmaf(rho, q0, hy.x), fmaf(rho, q1, hy.y));
@@ -480,14 +481,14 @@ __device__ __forceinline__ void row_update(float2 (&S)[64], rsrc_t sp, rsrc_t sp
         if (g == 0) w2x0 = wc[1].z;
 #pragma unroll
         for (int j = (g == 0 ? 1 : 0); j < CH; ++j) {
-            S[n0 - 1 + j] = finalize(wc[j], wc[j + 1], hc[j], hb, bot, rho);
+            S[n0 - 1 + j] = finalize(wc[j], wc[j + 1], hc[j], hb, rho);
             sched_fence();
         }
         wc[0] = wc[CH];
         hc[0] = hc[CH];
         sched_fence();
     }
-    S[63] = finalize(wc[0], make_float4(0.f, 0.f, w2x0, 0.f), hc[0], hb, bot, rho);
+    S[63] = finalize(wc[0], make_float4(0.f, 0.f, w2x0, 0.f), hc[0], hb, rho);
 #pragma unroll
     for (int m = 0; m < 16; ++m) S[m] = stg[m * kPT];
 #pragma unroll
@@ -845,12 +846,12 @@ __device__ __forceinline__ void row_adjoint(float2 (&S)[64], rsrc_t s1p, rsrc_t 
         if (n == 0) {
             w2x0 = nb4.z;
         } else {
-            S[n - 1] = finalize(wc[(n - 1) & 1], nb4, zero2, hb, bot, 1.0f);
+            S[n - 1] = finalize(wc[(n - 1) & 1], nb4, zero2, hb, 1.0f);
         }
         wc[n & 1] = nb4;
         sched_fence();
     }
-    S[63] = finalize(wc[1], make_float4(0.f, 0.f, w2x0, 0.f), zero2, hb, bot, 1.0f);
+    S[63] = finalize(wc[1], make_float4(0.f, 0.f, w2x0, 0.f), zero2, hb, 1.0f);
 #pragma unroll
     for (int m = 0; m < 16; ++m) S[m] = stg[m * kPT];
 #pragma unroll
