@@ -5,9 +5,11 @@
 // keeps the recordings registry (a replay must match its recording) and the profiler, and hands the call
 // to the launch sequencing (admm_launch.hip) with the plan of the path table (admm_paths.hip).  Nothing is
 // allocated and nothing synchronises unless the optional profiler is on.
-// Each single or grouped entry point fills a Call (and an adjoint a Grads, capi_internal.hpp) once; below that there is
-// one validation (check_call), one workspace carver (Carver; take_group_tables for the per-group table blocks), one
-// registry (rec_store / rec_forget / rec_take: nothing else locks it) and one adjoint (run_backward) for both families.
+// Each entry point fills a Call (and an adjoint a Grads, capi_internal.hpp) once -- the shape-only size queries with the
+// fields they have -- and plans it through forward_in / adjoint_in (admm_paths.hip), so a query, a workspace size and a
+// solve of the same call take the same plan.  Below that there is one validation (check_call), one workspace carver
+// (Carver; take_group_tables for the per-group table blocks), one registry (rec_store / rec_forget / rec_take: nothing
+// else locks it) and one adjoint (run_backward) for the single and the grouped family.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -93,26 +95,6 @@ int no_plane_mode(int iso, const char* who) {
 
 }  // namespace admm_capi
 
-using namespace admm_capi;
-
-extern "C" {
-
-int admm_abi_version(void) { return ADMM_ABI_VERSION; }
-
-int admm_iso_plane_supported(void) { return 1; }
-
-const char* admm_last_error(void) { return g_err.c_str(); }
-
-int admm_tvd_workspace_bytes(int M, int N, int P, int B, int kh, int kw, int iso, size_t* out_bytes) {
-    if (!out_bytes) return fail(ADMM_E_INVALID, "out_bytes is NULL");
-    int rc = check_shape(M, N, P, B, kh, kw, iso);
-    if (rc) return rc;
-    *out_bytes = forward_ws_bytes(M, N, (size_t)P * B, kh, iso);
-    return ADMM_OK;
-}
-
-}  // extern "C"
-
 namespace admm_capi {
 
 int check_ws(void* workspace, size_t have, size_t need) {
@@ -185,22 +167,22 @@ struct RecTag {
     int grouped, gb, gp, nparam;   // a grouped recording (admm_tvd_forward_grouped_record_dev_f32) and its grouping
     bool operator==(const RecTag& o) const { return std::memcmp(this, &o, sizeof(RecTag)) == 0; }
 };
-float g_dummy_scalar = 0.f;   // stands for "device-resident scalars" when a tag is rebuilt without them
 
 // the tag of a call: a single solve's has nbr = 1 and grouped = 0, a grouped call's its grouping, a multi-branch
-// recording's its branch count (set by forward_multi / backward_multi) -- no family replays another's recording
+// recording's its branch count (every branch's scalars are device-resident: a replay is not given them) -- no family
+// replays another's recording
 RecTag make_tag(const Call& c, bool want_h, bool masks) {
     RecTag t;
     std::memset(&t, 0, sizeof(t));
     t.M = c.M, t.N = c.N, t.P = c.P, t.B = c.B, t.kh = c.kh, t.kw = c.kw, t.maxit = c.maxit;
     t.iso = iso_plane(c.iso) ? ADMM_ISO_PLANE : c.iso != 0;   // the mode: no prox replays another's recording
     t.want_h = want_h, t.masks = masks;
-    t.nbr = 1;
-    t.dev_scalars = c.sc.lam != nullptr;
+    t.nbr = c.nbranch;
+    t.dev_scalars = c.sc.lam != nullptr || c.kind == kMulti;
     if (!t.dev_scalars) t.lam = c.sc.lam_v, t.rho = c.sc.rho_v;
     for (int i = 0; i < ADMM_OPT_COUNT; ++i) t.opts[i] = opt(i);
     t.sharded = c.red != nullptr;
-    t.grouped = c.grouped, t.gb = c.gb, t.gp = c.gp, t.nparam = c.nparam;
+    t.grouped = c.grouped(), t.gb = c.gb, t.gp = c.gp, t.nparam = c.nparam;
     return t;
 }
 
@@ -256,12 +238,22 @@ hipStream_t lib_stream(int i) {
     return v[i];
 }
 
-// forward workspace: one chunk layout, or one per stream of the MALL-resident schedule
-size_t forward_ws_bytes(int M, int N, size_t planes, int kh, int iso, const PathPlan* plp) {
-    const PathPlan pl = plp ? *plp : plan_paths(path_in(M, N, iso, kh > 0, ADMM_MODE_FORWARD, 0, false, false, planes));
-    const ChunkPlan cp = forward_chunks(M, N, planes, iso_batch(iso), pl.fwd, iso_plane(iso));
-    const size_t one = make_layout(M, N, cp.chunk, kh > 0, iso_batch(iso)).total;
-    return cp.streams > 1 ? (size_t)cp.streams * align_up(one) : one;
+// A plain forward as it will run: its path, its chunk schedule, the layout of one chunk and the workspace it needs (one
+// chunk layout, or one per stream of the MALL-resident schedule).
+struct FwdSetup {
+    PathPlan pl;
+    ChunkPlan cp;
+    Layout lay;
+    size_t bytes;
+};
+FwdSetup forward_setup(const Call& c) {
+    const PathIn q = forward_in(c);
+    FwdSetup f;
+    f.pl = plan_paths(q);
+    f.cp = forward_chunks(q, f.pl, c.planes());   // an isotropic batch is one chunk
+    f.lay = make_layout(c.M, c.N, f.cp.chunk, c.kh > 0, q.iso);
+    f.bytes = f.cp.streams > 1 ? (size_t)f.cp.streams * align_up(f.lay.total) : f.lay.total;
+    return f;
 }
 
 // ---- validation: one function for the single and the grouped family, forward (phases = 0) and adjoint ----
@@ -284,14 +276,46 @@ int check_grouped(int M, int N, int P, int B, int gb, int gp, int kh, int kw, in
     return ADMM_OK;
 }
 
+// the sizes, flags and options of a multi-branch call or workspace query
+int check_multi(int M, int N, int P, int B, int nbr, int maxit, int flags) {
+    if (P < 1 || B < 1 || nbr < 1) return fail(ADMM_E_INVALID, "sizes must be positive (P=%d B=%d nbranch=%d)", P, B, nbr);
+    if (maxit < 0) return fail(ADMM_E_INVALID, "maxit must be >= 0 (got %d)", maxit);
+    if (flags & ~(ADMM_MULTI_RECORD | ADMM_REC_MASKS | ADMM_MULTI_ISO)) return fail(ADMM_E_INVALID, "unknown flags 0x%x", flags);
+    if (M != kMultiM || N != kMultiN || !fused_enabled())
+        return fail(ADMM_E_UNSUPPORTED, "the multi-branch solve is the fused 256 x 256 kernels (got %d x %d%s); "
+                                        "solve the branches one by one", M, N, fused_enabled() ? "" : ", option FUSED = 0");
+    if ((flags & ADMM_MULTI_ISO) && (flags & ADMM_MULTI_RECORD) && !fused_adj_enabled())
+        return fail(ADMM_E_UNSUPPORTED, "an isotropic multi-branch recording needs the fused reverse sweep (option FUSED_ADJ)");
+    if ((size_t)P * B * nbr > kChunkPlanes)
+        return fail(ADMM_E_UNSUPPORTED, "at most %zu planes (nbranch * P * B) per multi-branch call", kChunkPlanes);
+    return ADMM_OK;
+}
+
 // phases: 0 = plain forward, else the adjoint's (run_backward); g: the adjoint's gradients (phases & 2: x_bar is read).
 // A grouped recording accepts ADMM_REC_MASKS without honouring it (the full trajectory is recorded, so rho_bar stays
-// available) and refuses unknown flag bits; a single recording's flags only plan.
+// available) and refuses unknown flag bits; a single recording's flags only plan.  A multi-branch call: phases 0 its
+// forward (recording or not), 2 the replay (its prox and masks flag are the recording's: c.flags is not checked).
 int check_call(const Call& c, int phases, const Grads* g, int rec_flags = 0) {
-    int rc = c.grouped ? check_grouped(c.M, c.N, c.P, c.B, c.gb, c.gp, c.kh, c.kw, c.iso)
-                       : check_shape(c.M, c.N, c.P, c.B, c.kh, c.kw, c.iso);
+    if (c.kind == kMulti) {
+        int rc = check_multi(c.M, c.N, c.P, c.B, c.nbranch, c.maxit, phases ? 0 : c.flags);
+        if (rc) return rc;
+        if (phases) {
+            if (!g->x_bar || !c.x_out || (reinterpret_cast<uintptr_t>(g->x_bar) & 15) ||
+                (reinterpret_cast<uintptr_t>(c.x_out) & 15) || (reinterpret_cast<uintptr_t>(g->y_bar) & 15))
+                return fail(ADMM_E_INVALID, "x_bar, x_out (and y_bar if given) must be 16-byte aligned device pointers");
+            return ADMM_OK;
+        }
+        rc = check_common(c.y, c.x_out, c.maxit);
+        if (rc) return rc;
+        if (!c.lam_b || !c.rho_b) return fail(ADMM_E_INVALID, "lambda and rho must be host arrays of nbranch device pointers");
+        for (int i = 0; i < c.nbranch; ++i)
+            if (!c.lam_b[i] || !c.rho_b[i]) return fail(ADMM_E_INVALID, "lambda[%d] / rho[%d] must be device pointers", i, i);
+        return ADMM_OK;
+    }
+    int rc = c.grouped() ? check_grouped(c.M, c.N, c.P, c.B, c.gb, c.gp, c.kh, c.kw, c.iso)
+                         : check_shape(c.M, c.N, c.P, c.B, c.kh, c.kw, c.iso);
     if (rc) return rc;
-    if (c.grouped) {
+    if (c.grouped()) {
         const char* who = phases ? "grouped adjoint" : "grouped solve";
         if (c.kh > 0 && !c.h) return fail(ADMM_E_INVALID, "%s: h is NULL with a %d x %d PSF", who, c.kh, c.kw);
         if (!c.sc.lam || !c.sc.rho) return fail(ADMM_E_INVALID, "%s: lambda and rho must be device pointers", who);
@@ -309,7 +333,7 @@ int check_call(const Call& c, int phases, const Grads* g, int rec_flags = 0) {
         return fail(ADMM_E_INVALID, "y_bar must be a 16-byte aligned device pointer (or NULL: not needed)");
     if ((phases & 2) && (!g->x_bar || (reinterpret_cast<uintptr_t>(g->x_bar) & 15)))
         return fail(ADMM_E_INVALID, "x_bar must be a 16-byte aligned device pointer");
-    if (phases && !c.grouped && c.planes() > 65535)
+    if (phases && !c.grouped() && c.planes() > 65535)
         return fail(ADMM_E_UNSUPPORTED, "the adjoint takes at most 65535 planes per call (split the batch)");
     return ADMM_OK;
 }
@@ -324,33 +348,26 @@ Call single_call(Call c) {
 int forward_impl(const Call& c) {
     int rc = check_call(c, 0, nullptr);
     if (rc) return rc;
-    const int M = c.M, N = c.N;
-    const bool iso = iso_batch(c.iso);
     const size_t planes = c.planes();
-    // a sharded isotropic solve plans without the plane-count rule: every shard must take the same path, since
-    // the fused and 2-pass kernels hand the reducer their sum maps in different layouts (lane-native float2 vs
-    // natural), and uneven shards can fall on either side of a threshold
-    const PathPlan pl = plan_paths(path_in(M, N, c.iso, c.kh > 0, ADMM_MODE_FORWARD, 0, false, false, c.red ? 0 : planes));
-    const ChunkPlan cp = forward_chunks(M, N, planes, iso, pl.fwd, iso_plane(c.iso));
-    const size_t chunk = cp.chunk;   // an isotropic batch is one chunk
-    const Layout lay = make_layout(M, N, chunk, c.kh > 0, iso);
-    rc = check_ws(c.workspace, c.workspace_bytes, forward_ws_bytes(M, N, planes, c.kh, c.iso, &pl));
+    const FwdSetup f = forward_setup(c);
+    const size_t chunk = f.cp.chunk;
+    rc = check_ws(c.workspace, c.workspace_bytes, f.bytes);
     if (rc) return rc;
     rec_forget(c.workspace);   // whatever was recorded there is overwritten now
     const hipStream_t s0 = reinterpret_cast<hipStream_t>(c.stream);
     unsigned char* ws = static_cast<unsigned char*>(c.workspace);
-    if (cp.streams <= 1) {
+    if (f.cp.streams <= 1) {
         Launcher ln{s0, g_prof.on, {}};
         // the tables (twiddles, C / G, scalars) once: later chunks reuse them from the same workspace
         for (size_t p0 = 0; p0 < planes && rc == 0; p0 += chunk)
-            rc = run_forward(ln, c, ws, lay, Traj{}, pl.fwd, p0 == 0, p0, std::min(chunk, planes - p0));
+            rc = run_forward(ln, c, ws, f.lay, Traj{}, f.pl.fwd, p0 == 0, p0, std::min(chunk, planes - p0));
         int rc2 = ln.finish();
         return rc ? rc : rc2;
     }
     // MALL-resident schedule: chunk i on stream i mod n (the caller's stream and n - 1 library streams), each stream
     // with its own chunk workspace; fork and join through events on the caller's stream
-    const int n = cp.streams;
-    const size_t stride = align_up(lay.total);
+    const int n = f.cp.streams;
+    const size_t stride = align_up(f.lay.total);
     std::vector<Launcher> lns;
     lns.reserve(n);
     lns.push_back(Launcher{s0, g_prof.on, {}});
@@ -370,7 +387,7 @@ int forward_impl(const Call& c) {
     for (size_t p0 = 0; p0 < planes && rc == 0; p0 += chunk, ++i) {
         const int k = (int)(i % (size_t)n);
         // each stream's chunk workspace builds the tables with its first chunk (96 setup launches per c4 solve -> 4)
-        rc = run_forward(lns[k], c, ws + (size_t)k * stride, lay, Traj{}, pl.fwd, i < (size_t)n, p0,
+        rc = run_forward(lns[k], c, ws + (size_t)k * stride, f.lay, Traj{}, f.pl.fwd, i < (size_t)n, p0,
                          std::min(chunk, planes - p0));
     }
     // join: the caller's stream waits for every library stream (also after an error, so nothing is left running
@@ -418,8 +435,7 @@ int forward_grouped(const Call& c) {
     if (rc) return rc;
     rec_forget(c.workspace);
     Launcher ln{reinterpret_cast<hipStream_t>(c.stream), g_prof.on, {}};
-    rc = run_forward(ln, c, static_cast<unsigned char*>(c.workspace), lay, Traj{},
-                     plan_grouped(c.M, c.N, iso_batch(c.iso), c.planes(), iso_plane(c.iso)));
+    rc = run_forward(ln, c, static_cast<unsigned char*>(c.workspace), lay, Traj{}, plan_paths(forward_in(c)).fwd);
     const int rc2 = ln.finish();
     return rc ? rc : rc2;
 }
@@ -466,7 +482,7 @@ int forward_state(Call c, const float* state_in, float* state_out, float* resid_
                      c.iso ? reinterpret_cast<float*>(ws + L.fmapK) : nullptr, reinterpret_cast<double*>(ws + L.rpart),
                      L.sK ? reinterpret_cast<float*>(ws + L.sK) : nullptr};
     c.st = &st;
-    return launch_forward_state(c, L, plan_state(c.M, c.N, c.iso != 0, c.planes()));
+    return launch_forward_state(c, L, plan_paths(forward_in(c)).fwd);
 }
 
 BwdLayout make_grouped_bwd_layout(const Call& c, bool want_h) {
@@ -494,6 +510,13 @@ BwdLayout make_grouped_bwd_layout(const Call& c, bool want_h) {
     return b;
 }
 
+// the adjoint workspace of a single or a grouped call planned as pl (mask bytes in place of s_k: anisotropic only)
+BwdLayout adjoint_layout(const Call& c, const PathPlan& pl) {
+    if (c.grouped()) return make_grouped_bwd_layout(c, pl.want_h);
+    const bool iso = iso_batch(c.iso);
+    return make_bwd_layout(c.M, c.N, c.planes(), c.kh, c.kw, c.maxit, pl.want_h, iso, pl.masks && !iso);
+}
+
 // The adjoint of a single or a grouped call.  phases: 1 = forward recording the trajectory into the workspace (writes
 // x_out), 2 = reverse sweep from a recorded workspace (x_out = that forward's output), 3 = both.  rec_flags
 // (ADMM_REC_*): phase 1 alone records the extra h_bar trajectory only when asked (phase 2 must then be given h_bar).
@@ -501,24 +524,14 @@ BwdLayout make_grouped_bwd_layout(const Call& c, bool want_h) {
 int run_backward(int phases, int rec_flags, const Call& c, const Grads& g) {
     int rc = check_call(c, phases, &g, rec_flags);
     if (rc) return rc;
-    const bool iso = iso_batch(c.iso);
     PathPlan plan;
     BwdLayout bl;
     RecTag tag;
     // plan, lay out, check the workspace, tag.  A replay (phase 2) is planned as the recording it replays was: masks
     // is the recording's flag (a replay whose options or arguments differ is rejected by its tag below).
     auto prepare = [&](bool masks) {
-        if (c.grouped) {
-            const bool want_h = phases == 1 ? (rec_flags & ADMM_REC_HBAR) != 0 : g.h_bar != nullptr;
-            plan = plan_grouped_adjoint(c.M, c.N, iso, c.kh > 0, c.planes(), want_h);
-            bl = make_grouped_bwd_layout(c, plan.want_h);
-        } else {
-            const int pflags = phases != 2 ? rec_flags : (g.h_bar ? ADMM_REC_HBAR : 0) | (masks ? ADMM_REC_MASKS : 0);
-            // sharded (c.red): no plane-count rule, so that every shard records and sweeps in one layout (forward_impl)
-            plan = plan_paths(path_in(c.M, c.N, c.iso, c.kh > 0, phases == 3 ? ADMM_MODE_BACKWARD : ADMM_MODE_RECORD, pflags,
-                                      g.h_bar != nullptr, g.rho_bar != nullptr, c.red ? 0 : c.planes()));
-            bl = make_bwd_layout(c.M, c.N, c.planes(), c.kh, c.kw, c.maxit, plan.want_h, iso, plan.masks && !iso);
-        }
+        plan = plan_paths(adjoint_in(c, phases, rec_flags, g, masks));
+        bl = adjoint_layout(c, plan);
         tag = make_tag(c, plan.want_h, plan.masks);
         return check_ws(c.workspace, c.workspace_bytes, bl.total);
     };
@@ -535,9 +548,9 @@ int run_backward(int phases, int rec_flags, const Call& c, const Grads& g) {
         if (!rec)
             return fail(ADMM_E_INVALID, "workspace holds no recording (%s first; a plain forward on the same workspace "
                                         "overwrites it)",
-                        c.grouped ? "admm_tvd_forward_grouped_record_dev_f32" : "admm_tvd_forward_record_*");
+                        c.grouped() ? "admm_tvd_forward_grouped_record_dev_f32" : "admm_tvd_forward_record_*");
         if (!(*rec == tag))
-            return c.grouped
+            return c.grouped()
                        ? fail(ADMM_E_INVALID, "replay does not match its grouped recording (shape, grouping gb / gp / nparam, "
                                               "PSF, iso, maxit, h_bar request or library options changed between record and "
                                               "replay, or the recording is a single solve's)")
@@ -559,20 +572,23 @@ size_t multi_F_bytes() { return align_up(admm::plane::tables_bytes()); }
 // tau_bar partial rows of one branch's isotropic sweep: 512 per reverse step k = K .. 2 (iso_radj_kernel)
 size_t multi_iso_rows(int K) { return (size_t)(K > 1 ? K - 1 : 1) * 512; }
 
-MultiLayout make_multi_layout(size_t planes, int nbr, int maxit, int flags) {
+// the workspace of a multi-branch call (c.flags: the forward's, or the recording's for its replay), for the grid it is
+// planned on
+MultiLayout make_multi_layout(const Call& c) {
     MultiLayout L{};
     Carver cv{0};
-    const size_t MN = (size_t)kMultiM * kMultiN;
-    const int K = maxit < 1 ? 1 : maxit;
+    const size_t MN = (size_t)kMultiM * kMultiN, planes = c.grid_planes();
+    const int nbr = c.nbranch, flags = c.flags, K = c.maxit < 1 ? 1 : c.maxit;
     const bool rec = (flags & ADMM_MULTI_RECORD) != 0, iso = (flags & ADMM_MULTI_ISO) != 0;
     const bool masks = (flags & ADMM_REC_MASKS) != 0 && !iso;
     L.prm = cv.take((size_t)nbr * 16);
     L.twM = cv.take(kMultiM * 8);
     L.twN = cv.take(kMultiN * 8);
     L.C = cv.take((size_t)nbr * multi_C_bytes());
-    L.two_pass = multi_two_pass(planes, flags);
+    const int fwd = plan_paths(forward_in(c)).fwd;
+    L.two_pass = fwd == ADMM_PATH_2PASS || fwd == ADMM_PATH_2PASS_ISO;
     if (L.two_pass) {
-        // the 2-pass kernels over every branch's planes (admm_launch.hip run_multi_2pass_*)
+        // the 2-pass kernels over every branch's planes (admm_launch.hip two_pass_multi)
         const size_t ppb = planes / (size_t)nbr;
         const int T = bwd_line_T(kMultiM, kMultiN, iso);
         if (iso) {
@@ -635,83 +651,49 @@ MultiLayout make_multi_layout(size_t planes, int nbr, int maxit, int flags) {
     return L;
 }
 
-int check_multi(int M, int N, int P, int B, int nbr, int maxit, int flags) {
-    if (P < 1 || B < 1 || nbr < 1) return fail(ADMM_E_INVALID, "sizes must be positive (P=%d B=%d nbranch=%d)", P, B, nbr);
-    if (maxit < 0) return fail(ADMM_E_INVALID, "maxit must be >= 0 (got %d)", maxit);
-    if (flags & ~(ADMM_MULTI_RECORD | ADMM_REC_MASKS | ADMM_MULTI_ISO)) return fail(ADMM_E_INVALID, "unknown flags 0x%x", flags);
-    if (M != kMultiM || N != kMultiN || !fused_enabled())
-        return fail(ADMM_E_UNSUPPORTED, "the multi-branch solve is the fused 256 x 256 kernels (got %d x %d%s); "
-                                        "solve the branches one by one", M, N, fused_enabled() ? "" : ", option FUSED = 0");
-    if ((flags & ADMM_MULTI_ISO) && (flags & ADMM_MULTI_RECORD) && !fused_adj_enabled())
-        return fail(ADMM_E_UNSUPPORTED, "an isotropic multi-branch recording needs the fused reverse sweep (option FUSED_ADJ)");
-    if ((size_t)P * B * nbr > kChunkPlanes)
-        return fail(ADMM_E_UNSUPPORTED, "at most %zu planes (nbranch * P * B) per multi-branch call", kChunkPlanes);
-    return ADMM_OK;
+// a multi-branch call's descriptor from the sizes and flags every entry of the family has: no PSF, the prox from flags
+Call multi_call(int M, int N, int P, int B, int nbranch, int maxit, int flags) {
+    Call c = shape_call(M, N, P, B, 0, 0, (flags & ADMM_MULTI_ISO) != 0, maxit);
+    c.kind = kMulti, c.nbranch = nbranch, c.flags = flags;
+    return c;
 }
 
-admm::plane::Branches multi_branches(int P, int B, int nbr) {
-    return admm::plane::Branches{P * B, nbr, P, (unsigned)(multi_F_bytes() / 4), 4u};
-}
-
-// the tag of a multi-branch recording (every branch's scalars are device-resident: a replay is not given them)
-RecTag multi_tag(int P, int B, int nbr, int iso, int maxit, bool masks) {
-    Call c{};
-    c.M = kMultiM, c.N = kMultiN, c.P = P, c.B = B, c.iso = iso, c.maxit = maxit;
-    c.sc = admm::ScalarSrc{&g_dummy_scalar, &g_dummy_scalar, 0.f, 0.f};
-    RecTag t = make_tag(c, false, masks);
-    t.nbr = nbr;
-    return t;
-}
-
-int forward_multi(const float* y, float* x_out, int M, int N, int P, int B, int nbr, const float* const* lambda,
-                  const float* const* rho, int maxit, int flags, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = check_multi(M, N, P, B, nbr, maxit, flags);
+int forward_multi(const Call& c) {
+    int rc = check_call(c, 0, nullptr);
     if (rc) return rc;
-    rc = check_common(y, x_out, maxit);
+    const MultiLayout L = make_multi_layout(c);
+    rc = check_ws(c.workspace, c.workspace_bytes, L.total);
     if (rc) return rc;
-    if (!lambda || !rho) return fail(ADMM_E_INVALID, "lambda and rho must be host arrays of nbranch device pointers");
-    for (int i = 0; i < nbr; ++i)
-        if (!lambda[i] || !rho[i]) return fail(ADMM_E_INVALID, "lambda[%d] / rho[%d] must be device pointers", i, i);
-    const size_t planes = (size_t)P * B * nbr;
-    const MultiLayout L = make_multi_layout(planes, nbr, maxit, flags);
-    rc = check_ws(workspace, workspace_bytes, L.total);
-    if (rc) return rc;
-    const int iso = (flags & ADMM_MULTI_ISO) != 0;
     // (masks: no rho_bar from the ST mask bits, nor from the isotropic recording)
-    if (flags & ADMM_MULTI_RECORD) rec_store(workspace, multi_tag(P, B, nbr, iso, maxit, (flags & ADMM_REC_MASKS) != 0 || iso));
-    else rec_forget(workspace);
-    return launch_forward_multi(y, x_out, M, N, P, B, nbr, lambda, rho, maxit, flags, workspace, stream, planes, L);
+    if (c.flags & ADMM_MULTI_RECORD) rec_store(c.workspace, make_tag(c, false, (c.flags & ADMM_REC_MASKS) != 0 || c.iso));
+    else rec_forget(c.workspace);
+    return launch_forward_multi(c, L);
 }
 
-int backward_multi(const float* x_bar, float* y_bar, float* lambda_bar, float* rho_bar, int M, int N, int P, int B,
-                   int nbr, int maxit, const float* x_out, void* workspace, size_t workspace_bytes, void* stream) {
-    int rc = check_multi(M, N, P, B, nbr, maxit, 0);
+// c.flags: none (a replay is not given them); the recording's prox and masks flag are taken from its tag
+int backward_multi(Call c, const Grads& g) {
+    int rc = check_call(c, 2, &g);
     if (rc) return rc;
-    if (!x_bar || !x_out || (reinterpret_cast<uintptr_t>(x_bar) & 15) || (reinterpret_cast<uintptr_t>(x_out) & 15) ||
-        (reinterpret_cast<uintptr_t>(y_bar) & 15))
-        return fail(ADMM_E_INVALID, "x_bar, x_out (and y_bar if given) must be 16-byte aligned device pointers");
-    int flags = ADMM_MULTI_RECORD;
-    rc = rec_take(workspace, [&](const RecTag* rec) -> int {
-        if (!rec || rec->nbr != nbr)
+    rc = rec_take(c.workspace, [&](const RecTag* rec) -> int {
+        if (!rec || rec->nbr != c.nbranch)
             return fail(ADMM_E_INVALID, "workspace holds no multi-branch recording of %d branches "
-                                        "(admm_tvd_forward_multi_dev_f32 with ADMM_MULTI_RECORD first)", nbr);
+                                        "(admm_tvd_forward_multi_dev_f32 with ADMM_MULTI_RECORD first)", c.nbranch);
         // the recording's prox and masks flag; everything else must be this call's
-        if (!(*rec == multi_tag(P, B, nbr, rec->iso, maxit, rec->masks != 0)))
+        c.iso = rec->iso;
+        c.flags = ADMM_MULTI_RECORD | (rec->iso ? ADMM_MULTI_ISO : 0) | (rec->masks ? ADMM_REC_MASKS : 0);
+        if (!(*rec == make_tag(c, false, rec->masks != 0)))
             return fail(ADMM_E_INVALID, "replay does not match its multi-branch recording (shape, maxit or library "
                                         "options changed)");
-        if (rec->masks && rho_bar)
+        if (rec->masks && g.rho_bar)
             return fail(ADMM_E_INVALID, "recorded with ADMM_REC_MASKS (soft-threshold branches only) or ADMM_MULTI_ISO: "
                                         "rho_bar cannot be formed from it");
-        flags |= (rec->iso ? ADMM_MULTI_ISO : 0) | (rec->masks ? ADMM_REC_MASKS : 0);
         return ADMM_OK;
     });
     if (rc) return rc;
-    const size_t planes = (size_t)P * B * nbr, ppb = (size_t)P * B, MN = (size_t)M * N;
-    const MultiLayout L = make_multi_layout(planes, nbr, maxit, flags);
-    rc = check_ws(workspace, workspace_bytes, L.total);
+    const MultiLayout L = make_multi_layout(c);
+    rc = check_ws(c.workspace, c.workspace_bytes, L.total);
     if (rc) return rc;
-    return launch_backward_multi(x_bar, y_bar, lambda_bar, rho_bar, M, N, P, B, nbr, maxit, x_out, workspace, stream,
-                                 flags, planes, ppb, MN, L);
+    return launch_backward_multi(c, g, L);
 }
 
 }  // namespace admm_capi
@@ -719,6 +701,20 @@ int backward_multi(const float* x_bar, float* y_bar, float* lambda_bar, float* r
 using namespace admm_capi;
 
 extern "C" {
+
+int admm_abi_version(void) { return ADMM_ABI_VERSION; }
+
+int admm_iso_plane_supported(void) { return 1; }
+
+const char* admm_last_error(void) { return g_err.c_str(); }
+
+int admm_tvd_workspace_bytes(int M, int N, int P, int B, int kh, int kw, int iso, size_t* out_bytes) {
+    if (!out_bytes) return fail(ADMM_E_INVALID, "out_bytes is NULL");
+    int rc = check_shape(M, N, P, B, kh, kw, iso);
+    if (rc) return rc;
+    *out_bytes = forward_setup(shape_call(M, N, P, B, kh, kw, iso)).bytes;
+    return ADMM_OK;
+}
 
 // The single-solve entry points: scalars checked, then Call / Grads filled in once.
 #define ADMM_SINGLE(sc, x, red) \
@@ -752,8 +748,8 @@ int admm_tvd_backward_workspace_bytes(int M, int N, int P, int B, int kh, int kw
     if (rc) return rc;
     if (maxit < 0) return fail(ADMM_E_INVALID, "maxit must be >= 0");
     if ((size_t)P * B > 65535) return fail(ADMM_E_UNSUPPORTED, "the adjoint takes at most 65535 planes per call (split the batch)");
-    const PathPlan pl = plan_paths(path_in(M, N, iso, kh > 0, ADMM_MODE_RECORD, want_hbar, false, false, (size_t)P * B));
-    *out_bytes = make_bwd_layout(M, N, (size_t)P * B, kh, kw, maxit, pl.want_h, iso_batch(iso), pl.masks && !iso).total;
+    const Call c = shape_call(M, N, P, B, kh, kw, iso, maxit);
+    *out_bytes = adjoint_layout(c, plan_paths(adjoint_in(c, 1, want_hbar, Grads{}))).total;
     return ADMM_OK;
 }
 
@@ -917,7 +913,7 @@ int admm_tvd_grouped_workspace_bytes(int M, int N, int P, int B, int gb, int gp,
 // The grouped entry points: one Call with the grouping, validated by check_call.
 #define ADMM_GROUPED(x)                                                                                             \
     Call{y, x, M, N, P, B, h, kh, kw, dev_sc(lambda, rho), iso, maxit, workspace, workspace_bytes, stream, nullptr, \
-         gb, gp, nparam, true}
+         gb, gp, nparam, kGrouped}
 
 int admm_tvd_forward_grouped_dev_f32(const float* y, float* x_out, int M, int N, int P, int B, int gb, int gp,
                                      const float* h, int kh, int kw, const float* lambda, const float* rho, int nparam,
@@ -932,15 +928,14 @@ int admm_tvd_grouped_backward_workspace_bytes(int M, int N, int P, int B, int gb
     if (rc) return rc;
     if (no_plane_mode(iso, "the grouped adjoint")) return ADMM_E_UNSUPPORTED;
     if (maxit < 0) return fail(ADMM_E_INVALID, "maxit must be >= 0");
-    const PathPlan pl = plan_grouped_adjoint(M, N, iso != 0, kh > 0, (size_t)P * B, (rec_flags & ADMM_REC_HBAR) != 0);
     // the larger of a pair per group (the larger (rho_bar, tau_bar) partial block) and one pair (more rows per part)
-    Call c{};
-    c.M = M, c.N = N, c.P = P, c.B = B, c.gb = gb, c.gp = gp, c.kh = kh, c.kw = kw, c.iso = iso, c.maxit = maxit;
-    c.grouped = true;
+    Call c = shape_call(M, N, P, B, kh, kw, iso, maxit);
+    c.kind = kGrouped, c.gb = gb, c.gp = gp;
+    const PathPlan pl = plan_paths(adjoint_in(c, 1, rec_flags, Grads{}));
     c.nparam = gb * gp;
-    const size_t a = make_grouped_bwd_layout(c, pl.want_h).total;
+    const size_t a = adjoint_layout(c, pl).total;
     c.nparam = 1;
-    const size_t b = make_grouped_bwd_layout(c, pl.want_h).total;
+    const size_t b = adjoint_layout(c, pl).total;
     *out_bytes = a > b ? a : b;
     return ADMM_OK;
 }
@@ -975,7 +970,7 @@ int admm_tvd_state_workspace_bytes(int M, int N, int P, int B, int kh, int kw, i
     if (no_plane_mode(iso, "the state call")) return ADMM_E_UNSUPPORTED;
     // (the plain forward of the same arguments fits too: its MALL chunk schedule never needs more than the whole batch)
     *out_bytes = std::max(make_state_layout(M, N, (size_t)P * B, kh > 0, iso != 0).total,
-                          forward_ws_bytes(M, N, (size_t)P * B, kh, iso != 0));
+                          forward_setup(shape_call(M, N, P, B, kh, kw, iso)).bytes);
     return ADMM_OK;
 }
 
@@ -986,7 +981,7 @@ int admm_tvd_forward_state_dev_f32(const float* y, float* x_out, int M, int N, i
     const int rc = check_dev_scalars(lambda, rho);
     if (rc) return rc;
     return forward_state(Call{y, x_out, M, N, P, B, h, kh, kw, dev_sc(lambda, rho), iso, maxit, workspace, workspace_bytes,
-                              stream, nullptr},
+                              stream, nullptr, 1, 1, 1, kState},
                          state_in, state_out, resid_out);
 }
 
@@ -994,21 +989,26 @@ int admm_tvd_multi_workspace_bytes(int M, int N, int P, int B, int nbranch, int 
     if (!out_bytes) return fail(ADMM_E_INVALID, "out_bytes is NULL");
     int rc = check_multi(M, N, P, B, nbranch, maxit, flags);
     if (rc) return rc;
-    *out_bytes = make_multi_layout((size_t)P * B * nbranch, nbranch, maxit, flags).total;
+    *out_bytes = make_multi_layout(multi_call(M, N, P, B, nbranch, maxit, flags)).total;
     return ADMM_OK;
 }
 
 int admm_tvd_forward_multi_dev_f32(const float* y, float* x_out, int M, int N, int P, int B, int nbranch,
                                    const float* const* lambda, const float* const* rho, int maxit, int flags,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-    return forward_multi(y, x_out, M, N, P, B, nbranch, lambda, rho, maxit, flags, workspace, workspace_bytes, stream);
+    Call c = multi_call(M, N, P, B, nbranch, maxit, flags);
+    c.y = y, c.x_out = x_out, c.lam_b = lambda, c.rho_b = rho;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
+    return forward_multi(c);
 }
 
 int admm_tvd_backward_multi_recorded_dev_f32(const float* x_bar, float* y_bar, float* lambda_bar, float* rho_bar, int M,
                                              int N, int P, int B, int nbranch, int maxit, const float* x_out,
                                              void* workspace, size_t workspace_bytes, void* stream) {
-    return backward_multi(x_bar, y_bar, lambda_bar, rho_bar, M, N, P, B, nbranch, maxit, x_out, workspace,
-                          workspace_bytes, stream);
+    Call c = multi_call(M, N, P, B, nbranch, maxit, 0);
+    c.x_out = const_cast<float*>(x_out);   // (a replay reads x_out, the recorded forward's output)
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = stream;
+    return backward_multi(c, Grads{x_bar, y_bar, nullptr, lambda_bar, rho_bar});
 }
 
 }  // extern "C"

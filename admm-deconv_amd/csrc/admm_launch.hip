@@ -16,7 +16,8 @@
 //   launch_*_multi       the one-grid multi-branch solve: the fused kernels, or the same TwoPass sequences
 //   launch_forward_state the resumable solve: the forward from s_0 (state_start: v_0 in place of the cleared first line
 //                        spectrum) or from the zero state, then the end kernels (s_K, residual norms; state_kernels.hip)
-// A call arrives as the Call / Grads descriptors of capi_internal.hpp, never as a positional parameter list.
+// A call of any family arrives as the Call / Grads descriptors of capi_internal.hpp, never as a positional parameter
+// list, with the plan (PathPlan, or the layout planned for it) that plan_paths made of it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -459,19 +460,24 @@ TwoPass two_pass_single(Launcher& ln, int M, int N, size_t planes, int T, const 
     return c;
 }
 
-// ---- several branches below the plane-count rule: the 2-pass kernels over every branch's planes ----
-Branches multi2_branches(int P, int B, int nbr) { return Branches{P * B, nbr, P, (unsigned)(multi_C_bytes() / 4), 4u}; }
+// ---- several branches in one grid: the kernels' descriptor over the fused grid's lane-native tables or the 2-pass
+// grid's C tables, and the 2-pass grid over every branch's planes ----
+Branches multi_branches(const Call& m, size_t table_bytes) {
+    return Branches{m.P * m.B, m.nbranch, m.P, (unsigned)(table_bytes / 4), 4u};
+}
 
-TwoPass two_pass_multi(Launcher& ln, int P, int B, int nbr, size_t planes, int T, unsigned char* ws, const MultiLayout& Ly) {
-    TwoPass c = two_pass_grid(ln, kMultiM, kMultiN, planes, T);
+TwoPass two_pass_multi(Launcher& ln, const Call& m, int T, const MultiLayout& Ly) {
+    unsigned char* ws = static_cast<unsigned char*>(m.workspace);
+    const int nbr = m.nbranch;
+    TwoPass c = two_pass_grid(ln, kMultiM, kMultiN, m.grid_planes(), T);
     const MultiView v = view(ws, Ly);
     c.twM = v.twM, c.twN = v.twN, c.C = at<float>(ws, Ly.C), c.G = nullptr, c.prm = v.prm;
     // H^T y = y (no PSF) in the spectral domain: Y_h = F y per grid plane in the hln slot, unused by the 2-pass grid
     c.spec0 = at<float2>(ws, Ly.spec0), c.spec1 = at<float2>(ws, Ly.spec1), c.yh = v.hln;
-    c.br = c.bro = multi2_branches(P, B, nbr);
+    c.br = c.bro = multi_branches(m, multi_C_bytes());
     c.map_in = kMapIn, c.map_out = kMapOut;
     c.fmap = v.fmap, c.qpart = v.qpart;
-    c.ng = nbr * Ly.ngb, c.Gp = Ly.G, c.ngb = c.ngb_k = Ly.ngb, c.gplanes = P * B;
+    c.ng = nbr * Ly.ngb, c.Gp = Ly.G, c.ngb = c.ngb_k = Ly.ngb, c.gplanes = m.P * m.B;
     c.ny = (unsigned)nbr, c.prm_f = 4u, c.nstride = (size_t)nbr * c.MN;
     c.rows = Ly.rows_b, c.pbs = Ly.pbs, c.r_off = Ly.nblk_a;
     return c;
@@ -646,7 +652,7 @@ int run_forward_generic(Launcher& ln, const Call& c, const PlaneRange& r, const 
 // a grouped call's descriptor for the 2-pass / runtime-length kernels (C / G tables group_tab_f apart, a scalar block per
 // group when it has a (lambda, rho) pair per group); a single solve: kOneSolve
 Branches call_branches(const Call& c) {
-    if (!c.grouped) return kOneSolve;
+    if (!c.grouped()) return kOneSolve;
     return admm::plane::grouped_branches(c.P, c.B, c.gb, c.gp, group_tab_f(c.M, c.N), c.nparam > 1 ? 4u : 0u);
 }
 
@@ -663,7 +669,7 @@ int run_forward(Launcher& ln, const Call& c, unsigned char* ws, const Layout& la
     const admm_batch_reducer* red = c.red;
     const FwdView v = view(ws, lay, kh > 0);
     const int L = M / 2;
-    const bool grp = c.grouped;
+    const bool grp = c.grouped();
     const Branches br = call_branches(c);
     if (tables) rc = ln.run(ADMM_K_SETUP, [&] {
         const size_t lds = (size_t)(M + N) * 16 + (kh * kw <= admm::kSetupPsfLds ? (size_t)kh * kw * 4 : 0);
@@ -1246,7 +1252,7 @@ struct Grouping {
     bool on() const { return br.nbr == 0; }
 };
 Grouping grouping_of(const Call& c, const BwdLayout& bl, unsigned char* ws) {
-    if (!c.grouped) return Grouping{kOneSolve, 1, 1, 0u, 1, 1, nullptr};
+    if (!c.grouped()) return Grouping{kOneSolve, 1, 1, 0u, 1, 1, nullptr};
     return Grouping{call_branches(c), c.groups(), c.nparam, group_tab_f(c.M, c.N), bl.split_rt, bl.split_h,
                     at<double>(ws, bl.gtmp)};
 }
@@ -1325,7 +1331,7 @@ int assemble_grads(Launcher& ln, const BwdView& v, const BwdLayout& bl, const Ca
 }
 
 // The adjoint of a single or a grouped call: one recording forward, one reverse sweep over every plane (a grouped
-// call's with its group's tables and scalars; plan: plan_paths or plan_grouped_adjoint), then the assembly.
+// call's with its group's tables and scalars; plan: plan_paths'), then the assembly.
 int launch_backward(int phases, const Call& c, const Grads& g, const PathPlan& plan, const BwdLayout& bl) {
     int rc = ADMM_OK;
     unsigned char* ws = static_cast<unsigned char*>(c.workspace);
@@ -1421,18 +1427,20 @@ int launch_backward(int phases, const Call& c, const Grads& g, const PathPlan& p
 }
 
 // ---- several branches in one grid ----------------------------------------------------------------------------
-int launch_forward_multi(const float* y, float* x_out, int M, int N, int P, int B, int nbr, const float* const* lambda,
-                         const float* const* rho, int maxit, int flags, void* workspace, void* stream, size_t planes,
-                         const MultiLayout& L) {
+int launch_forward_multi(const Call& c, const MultiLayout& L) {
     int rc = ADMM_OK;
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    unsigned char* ws = static_cast<unsigned char*>(c.workspace);
+    hipStream_t s = reinterpret_cast<hipStream_t>(c.stream);
     Launcher ln{s, g_prof.on, {}};
+    const float* y = c.y;
+    float* x_out = c.x_out;
+    const int M = c.M, N = c.N, nbr = c.nbranch, maxit = c.maxit, flags = c.flags;
+    const size_t planes = c.grid_planes();
     const MultiView v = view(ws, L);
     for (int i = 0; i < nbr; ++i) {
         float* Ct = at<float>(ws, L.C + (size_t)i * multi_C_bytes());
         void* F = ws + L.F + (size_t)i * multi_F_bytes();
-        const admm::ScalarSrc sc{lambda[i], rho[i], 0.f, 0.f};
+        const admm::ScalarSrc sc{c.lam_b[i], c.rho_b[i], 0.f, 0.f};
         rc = ln.run(ADMM_K_SETUP, [&] {
             const size_t lds = (size_t)(M + N) * 16;
             const int nb = (int)(((size_t)(M / 2 + 1) * N + kThreads - 1) / kThreads);
@@ -1459,12 +1467,12 @@ int launch_forward_multi(const float* y, float* x_out, int M, int N, int P, int 
         tr.s = rec ? reinterpret_cast<float*>(v.traj) : nullptr;
         tr.nrm = rec && iso ? v.nrm : nullptr;
         float* sA = rec ? nullptr : at<float>(ws, L.sA);
-        rc = two_pass_forward(two_pass_multi(ln, P, B, nbr, planes, line_T(M, N), ws, L), y, x_out, maxit, iso, tr, sA,
+        rc = two_pass_forward(two_pass_multi(ln, c, line_T(M, N), L), y, x_out, maxit, iso, tr, sA,
                               rec || iso ? sA : at<float>(ws, L.sbA));
         if (rc) return rc;
         return ln.finish();
     }
-    const admm::plane::Branches br = multi_branches(P, B, nbr);
+    const admm::plane::Branches br = multi_branches(c, multi_F_bytes());
     if (iso) {
         // each branch's batch norm over its own planes; recording: s_{k+1} into slot k, |s_{k+1}| too
         const size_t kE = (size_t)M * N / 2;
@@ -1484,14 +1492,15 @@ int launch_forward_multi(const float* y, float* x_out, int M, int N, int P, int 
     return ln.finish();
 }
 
-int launch_backward_multi(const float* x_bar, float* y_bar, float* lambda_bar, float* rho_bar, int M, int N, int P,
-                          int B, int nbr, int maxit, const float* x_out, void* workspace, void* stream, int flags,
-                          size_t planes, size_t ppb, size_t MN, const MultiLayout& L) {
+int launch_backward_multi(const Call& c, const Grads& g, const MultiLayout& L) {
     int rc = ADMM_OK;
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    unsigned char* ws = static_cast<unsigned char*>(c.workspace);
+    hipStream_t s = reinterpret_cast<hipStream_t>(c.stream);
     Launcher ln{s, g_prof.on, {}};
-    const int K = maxit;
+    const float *x_bar = g.x_bar, *x_out = c.x_out;
+    float *y_bar = g.y_bar, *lambda_bar = g.lambda_bar, *rho_bar = g.rho_bar;
+    const int M = c.M, N = c.N, nbr = c.nbranch, K = c.maxit, flags = c.flags;
+    const size_t planes = c.grid_planes(), ppb = c.planes(), MN = (size_t)M * N;
     if (K == 0) {
         if (y_bar) HIPCHK(hipMemsetAsync(y_bar, 0, ppb * MN * 4, s));
         if (lambda_bar) HIPCHK(hipMemsetAsync(lambda_bar, 0, (size_t)nbr * 4, s));
@@ -1507,13 +1516,13 @@ int launch_backward_multi(const float* x_bar, float* y_bar, float* lambda_bar, f
         // k = 1 launches no ISO_ADJ_R: its partial rows must read as zero
         if (iso) HIPCHK(hipMemsetAsync(v.part, 0, (size_t)nbr * L.pbs * 8, s));
         if (b.vsum) HIPCHK(hipMemsetAsync(b.vsum, 0, planes * MN * 4, s));
-        rc = two_pass_reverse(two_pass_multi(ln, P, B, nbr, planes, bwd_line_T(M, N, iso), ws, L), b, x_bar, K, iso, false);
+        rc = two_pass_reverse(two_pass_multi(ln, c, bwd_line_T(M, N, iso), L), b, x_bar, K, iso, false);
         if (rc) return rc;
         rc = branch_grads(ln, v, L.pbs, K * L.rows_b, lambda_bar, rho_bar, b.vsum, y_bar, ppb * MN, nbr);
         if (rc) return rc;
         return ln.finish();
     }
-    const admm::plane::Branches br = multi_branches(P, B, nbr);
+    const admm::plane::Branches br = multi_branches(c, multi_F_bytes());
     // each branch's Vsum in the natural layout (per grid plane): the forward's H^T y copies are dead
     float* vout = y_bar ? reinterpret_cast<float*>(v.hln) : nullptr;
     if (iso) {

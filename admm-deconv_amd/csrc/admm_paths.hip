@@ -1,6 +1,8 @@
 // admm_paths.hip -- the path decision table and the library options (host code only; see capi_internal.hpp).
-// Which kernels a call runs is decided in plan_paths and nowhere else; admm_launch.hip executes the plan and
-// admm_query_paths returns it to tests without a GPU.  The tile-size policy of the 2-pass and runtime-length
+// Which kernels a call runs -- single, grouped, state or multi-branch, either isotropic mode -- is decided in plan_paths
+// and nowhere else: two rule lists (reverse sweep, forward), each rule with the capabilities of its kernels.
+// forward_in / adjoint_in are the one way from a Call to the table's input; admm_launch.hip executes the plan and the
+// admm_query_* entries return it to tests without a GPU.  The tile-size policy of the 2-pass and runtime-length
 // kernels lives here too: the workspace layouts (admm_capi.hip) and the launches (admm_launch.hip) share it.
 #include <hip/hip_runtime.h>
 
@@ -103,14 +105,14 @@ bool enough_planes(const PathIn& q, MinPlanesFor which) {
 // streams 97-149 ms, profiles/r06_c4_mall_streams_sweep.txt -- their 4-5 plane chunks are too small: 4 x 4 97.0,
 // 5 x 4 85.3 ms; with 8 hardware queues 6 / 8 streams are slower still, profiles/r06_c4_hw_queues_probe.txt).
 // The smooth-length 2-pass kernels gain the same way (480 x 640 x 64 / 256 +5 / +7 %, 384^2 x 512 +11 %).
-ChunkPlan forward_chunks(int M, int N, size_t planes, bool iso, int fwd_path, bool bt) {
-    const size_t base = chunk_planes(planes, iso);
-    if (bt) return {base, 1};   // ADMM_ISO_PLANE: plain chunks, never the MALL schedule
+ChunkPlan forward_chunks(const PathIn& q, const PathPlan& pl, size_t planes) {
+    const size_t base = chunk_planes(planes, q.iso);
+    if (q.bt) return {base, 1};   // ADMM_ISO_PLANE: plain chunks, never the MALL schedule
     const int n = opt(ADMM_OPT_MALL_STREAMS);
-    const bool two_pass = fwd_path == ADMM_PATH_2PASS || fwd_path == ADMM_PATH_SMOOTH || fwd_path == ADMM_PATH_RUNTIME;
-    if (iso || n <= 1 || !two_pass) return {base, 1};
+    const bool two_pass = pl.fwd == ADMM_PATH_2PASS || pl.fwd == ADMM_PATH_SMOOTH || pl.fwd == ADMM_PATH_RUNTIME;
+    if (q.iso || n <= 1 || !two_pass) return {base, 1};
     constexpr size_t kMall = size_t(256) << 20, kBudget = size_t(224) << 20;
-    const size_t per_plane = 28 * (size_t)M * N;
+    const size_t per_plane = 28 * (size_t)q.M * q.N;
     if (planes * per_plane <= 2 * kMall) return {base, 1};
     size_t chunk = kBudget / ((size_t)n * per_plane);
     // chunks of 1-2 large planes lose (2048^2 x 8: 1-plane chunks -15 %, 1000^2 x 64: 2-plane chunks -2 %;
@@ -120,141 +122,142 @@ ChunkPlan forward_chunks(int M, int N, size_t planes, bool iso, int fwd_path, bo
     return {chunk, n > 16 ? 16 : n};
 }
 
-// Several 256 x 256 branches in one grid (admm_tvd_forward_multi_dev_f32): the per-plane kernels from the fused
-// paths' plane counts in all (kMinFused / kMinFusedIso), below them the 2-pass kernels over every branch's planes
-// (the c5 training step at batch 2 has 30: tools/small_batch_probe.py, profiles/r05_small_batch_probe.jsonl).
-bool multi_two_pass(size_t planes, int flags) {
-    const bool iso = (flags & ADMM_MULTI_ISO) != 0;
-    return !enough_planes(PathIn{kMultiM, kMultiN, iso, false, ADMM_MODE_FORWARD, 0, false, false, planes},
-                          iso ? kMinFusedIso : kMinFused);
-}
-TrajFlags traj_flags(const PathIn& q, const PathPlan& pl) {
-    if (q.mode == ADMM_MODE_FORWARD) return {false, false, false, false, false};
-    return {true, pl.want_h, q.iso, pl.masks && !q.iso, pl.iso_lane};
-}
-// forward rules, first match wins
-struct FwdRule {
+// ---- the decision table ------------------------------------------------------------------------------------------
+// Two rule lists, the reverse sweep's and the forward's, first match wins.  A rule is a kernel family: `takes` is what
+// its kernels can be handed (PathCap: a plane -> group map, a caller-given s_0, ADMM_ISO_PLANE, several branches in one
+// grid), `applies` when they are the choice for a shape, a prox, the options and a plane count.  A call family
+// (grouped, state, multi-branch; ADMM_ISO_PLANE) has no rules of its own: it is planned on the rules that take all it
+// needs.  A new family is one more capability bit, set on the rules whose kernels were taught it.
+struct Rule {
     int path;
+    unsigned takes;
     bool (*applies)(const PathIn&, const TrajFlags&);
 };
-const FwdRule kFwdRules[] = {
+bool takes(const Rule& r, const PathIn& q) { return (q.needs() & ~r.takes) == 0; }
+// the masks / lane-native isotropic trajectory: asked for by a recording (ADMM_REC_MASKS), taken by the combined call
+// whenever rho_bar is not wanted
+bool masks_asked(const PathIn& q) { return q.mode == ADMM_MODE_RECORD ? (q.rec_flags & ADMM_REC_MASKS) != 0 : !q.rho_bar; }
+
+// The reverse sweep is chosen first: the trajectory it reads is what the forward must record (t.v: the dim-2 spectra of
+// an h_bar recording, which only the 2-pass and runtime-length column passes keep).
+const Rule kBwdRules[] = {
+    // plane256_adj_kernel: the fused 256 x 256 forward's lane-native s_k, or their ST mask bits (one table set per
+    // branch: no group map)
+    {ADMM_PATH_SWEEP_FUSED, kCapBranches, [](const PathIn& q, const TrajFlags& t) {
+         return fused_shape(q.M, q.N, q.iso) && !t.v && fused_enabled() && fused_adj_enabled() && enough_planes(q, kMinFused);
+     }},
+    // plane256_isoadj: the split-iteration trajectory (s and |s| lane-native); rho_bar cannot be formed from it, so only
+    // where the masks flag allows
+    {ADMM_PATH_SWEEP_FUSED_ISO, kCapBranches, [](const PathIn& q, const TrajFlags& t) {
+         return q.iso && fused_tables_shape(q.M, q.N) && !t.v && fused_enabled() && fused_adj_enabled() &&
+                enough_planes(q, kMinFusedIso) && masks_asked(q);
+     }},
+    {ADMM_PATH_SWEEP_RUNTIME_ISO, kCapGroups, [](const PathIn& q, const TrajFlags&) { return q.iso && generic_shape(q.M, q.N); }},
+    {ADMM_PATH_SWEEP_RUNTIME, kCapGroups | kCapPlaneBT, [](const PathIn& q, const TrajFlags&) { return generic_shape(q.M, q.N); }},
+    {ADMM_PATH_SWEEP_2PASS_ISO, kCapGroups | kCapBranches, [](const PathIn& q, const TrajFlags&) { return q.iso; }},
+    // (also of a fused forward's lane-native trajectory: PathPlan::ln_traj)
+    {ADMM_PATH_SWEEP_2PASS, kCapGroups | kCapPlaneBT | kCapBranches, [](const PathIn&, const TrajFlags&) { return true; }},
+};
+
+const Rule kFwdRules[] = {
     // runtime-length shapes: the CU-resident solve (admm_resident.hip) where compiled and measured faster,
     // anisotropic and recording neither dim-2 spectra, norms nor mask bits (it writes s_k into the slots)
     // (and the small power-of-two squares it compiled: 32, 64, 128; it needs no spectra buffers, so it runs on
     // either layout)
-    {ADMM_PATH_RESIDENT, [](const PathIn& q, const TrajFlags& t) {
+    {ADMM_PATH_RESIDENT, 0, [](const PathIn& q, const TrajFlags& t) {
          return !q.iso && !t.v && !t.nrm && !t.m && opt(ADMM_OPT_RESIDENT) != 0 &&
                 (!generic_shape(q.M, q.N) || opt(ADMM_OPT_SMOOTH) != 0) &&
                 admm::rs::has_shape(q.M, q.N, opt(ADMM_OPT_RESIDENT) >= 2) && enough_planes(q, kMinResident);
      }},
     // isotropic: the split-iteration CU-resident solve (resident_iso_kernel, one launch per iteration with the
     // norm kernel between); it records s_k and |s_k| in the natural layout the 2-pass / runtime sweeps read
-    {ADMM_PATH_RESIDENT_ISO, [](const PathIn& q, const TrajFlags& t) {
+    {ADMM_PATH_RESIDENT_ISO, 0, [](const PathIn& q, const TrajFlags& t) {
          return q.iso && !t.v && opt(ADMM_OPT_RESIDENT) != 0 && (!generic_shape(q.M, q.N) || opt(ADMM_OPT_SMOOTH) != 0) &&
                 admm::rs::has_iso_shape(q.M, q.N, opt(ADMM_OPT_RESIDENT) >= 2) && enough_planes(q, kMinResidentIso);
      }},
     // compile-time-plan kernels when this build has either length (admm_smooth.hip), else runtime plans
-    {ADMM_PATH_SMOOTH, [](const PathIn& q, const TrajFlags&) {
+    {ADMM_PATH_SMOOTH, 0, [](const PathIn& q, const TrajFlags&) {
          return generic_shape(q.M, q.N) && opt(ADMM_OPT_SMOOTH) != 0 &&
                 (admm::sm::has_length(q.M) || admm::sm::has_length(q.N));
      }},
-    {ADMM_PATH_RUNTIME, [](const PathIn& q, const TrajFlags&) { return generic_shape(q.M, q.N); }},
-    // 256 x 256 anisotropic: one workgroup per plane runs all K iterations (plane_kernel.hip)
-    {ADMM_PATH_FUSED, [](const PathIn& q, const TrajFlags& t) {
+    {ADMM_PATH_RUNTIME, kCapGroups | kCapState | kCapPlaneBT,
+     [](const PathIn& q, const TrajFlags&) { return generic_shape(q.M, q.N); }},
+    // 256 x 256 anisotropic: one workgroup per plane runs all K iterations (plane_kernel.hip; its grouped recording and
+    // state instances: plane_grouped_rec.hip, plane_state.hip)
+    {ADMM_PATH_FUSED, kCapGroups | kCapState | kCapBranches, [](const PathIn& q, const TrajFlags& t) {
          return fused_shape(q.M, q.N, q.iso) && !t.v && fused_enabled() && enough_planes(q, kMinFused);
      }},
     // 256 x 256 isotropic: split-iteration per-plane kernels (plane_iso.hip); a recording only in its own
     // lane-native layout (the fused sweep's)
-    {ADMM_PATH_FUSED_ISO, [](const PathIn& q, const TrajFlags& t) {
+    {ADMM_PATH_FUSED_ISO, kCapBranches, [](const PathIn& q, const TrajFlags& t) {
          return q.iso && fused_tables_shape(q.M, q.N) && (!t.s || t.iso_lane) && !t.v && fused_enabled() &&
                 enough_planes(q, kMinFusedIso);
      }},
-    {ADMM_PATH_2PASS_ISO, [](const PathIn& q, const TrajFlags&) { return q.iso; }},
-    {ADMM_PATH_2PASS, [](const PathIn&, const TrajFlags&) { return true; }},
+    // the 2-pass kernels: every tuned shape and family, several 256 x 256 branches in one grid included (below the fused
+    // kernels' plane counts over all branches: the c5 training step at batch 2 has 30, tools/small_batch_probe.py,
+    // profiles/r05_small_batch_probe.jsonl)
+    {ADMM_PATH_2PASS_ISO, kCapGroups | kCapState | kCapBranches, [](const PathIn& q, const TrajFlags&) { return q.iso; }},
+    {ADMM_PATH_2PASS, kCapGroups | kCapState | kCapPlaneBT | kCapBranches,
+     [](const PathIn&, const TrajFlags&) { return true; }},
 };
+
+template <size_t n>
+int first_rule(const Rule (&rules)[n], const PathIn& q, const TrajFlags& t) {
+    for (const Rule& r : rules)
+        if (takes(r, q) && r.applies(q, t)) return r.path;
+    return 0;
+}
 
 PathPlan plan_paths(const PathIn& q) {
     PathPlan pl;
-    const bool rec = q.mode != ADMM_MODE_FORWARD;
-    if (q.bt) {
-        // ADMM_ISO_PLANE: the block-threshold line kernels exist on the 2-pass and the runtime-length grid only, and
-        // the path never depends on the plane count or the options (a plane's result does not depend on its batch);
-        // the recording is the natural-layout s_k (ADMM_REC_MASKS accepted, not honoured)
-        const bool gen = generic_shape(q.M, q.N);
-        pl.fwd = gen ? ADMM_PATH_RUNTIME : ADMM_PATH_2PASS;
-        if (rec) {
-            pl.want_h = (q.mode == ADMM_MODE_RECORD ? (q.rec_flags & ADMM_REC_HBAR) != 0 : q.h_bar) && q.psf;
-            pl.bwd = gen ? ADMM_PATH_SWEEP_RUNTIME : ADMM_PATH_SWEEP_2PASS;
-        }
-        return pl;
-    }
-    if (rec) {
+    TrajFlags t{false, false, false, false, false};
+    if (q.mode != ADMM_MODE_FORWARD) {
         pl.want_h = (q.mode == ADMM_MODE_RECORD ? (q.rec_flags & ADMM_REC_HBAR) != 0 : q.h_bar) && q.psf;
-        // the fused kernel records s in its lane-native layout (no dim-2 spectra: not with h_bar)
-        pl.ln_traj = fused_shape(q.M, q.N, q.iso) && fused_enabled() && !pl.want_h && enough_planes(q, kMinFused);
-        // mask-bit trajectory (fused forward + fused reverse sweep): asked for by a recording (ADMM_REC_MASKS),
-        // taken by the combined call whenever rho_bar is not wanted; isotropic at 256 x 256 the same flag
-        // selects the split-iteration trajectory (s and |s| lane-native) for the fused isotropic sweep
-        const bool iso_ok = q.iso && fused_tables_shape(q.M, q.N) && !pl.want_h && fused_enabled() && fused_adj_enabled() &&
-                            enough_planes(q, kMinFusedIso);
-        const bool masks_ok = (pl.ln_traj && !q.iso && fused_adj_enabled()) || iso_ok;
-        pl.masks = masks_ok && (q.mode == ADMM_MODE_RECORD ? (q.rec_flags & ADMM_REC_MASKS) != 0 : !q.rho_bar);
-        pl.iso_lane = pl.masks && q.iso;
+        t = TrajFlags{true, pl.want_h, q.iso, false, false};
+        pl.bwd = first_rule(kBwdRules, q, t);
+        // what the fused sweeps read instead of the natural-layout s_k: mask bits where asked for (anisotropic), the
+        // split-iteration trajectory (isotropic)
+        pl.iso_lane = pl.bwd == ADMM_PATH_SWEEP_FUSED_ISO;
+        pl.masks = pl.iso_lane || (pl.bwd == ADMM_PATH_SWEEP_FUSED && masks_asked(q));
+        t.m = pl.masks && !q.iso, t.iso_lane = pl.iso_lane;
     }
-    const TrajFlags t = traj_flags(q, pl);
-    for (const FwdRule& r : kFwdRules)
-        if (r.applies(q, t)) {
-            pl.fwd = r.path;
-            break;
-        }
-    if (rec) {
-        if (pl.ln_traj && !q.iso && fused_adj_enabled()) pl.bwd = ADMM_PATH_SWEEP_FUSED;         // plane256_adj_kernel
-        else if (pl.iso_lane) pl.bwd = ADMM_PATH_SWEEP_FUSED_ISO;                                   // plane256_isoadj
-        else if (generic_shape(q.M, q.N)) pl.bwd = q.iso ? ADMM_PATH_SWEEP_RUNTIME_ISO : ADMM_PATH_SWEEP_RUNTIME;
-        else pl.bwd = q.iso ? ADMM_PATH_SWEEP_2PASS_ISO : ADMM_PATH_SWEEP_2PASS;
-    }
+    pl.fwd = first_rule(kFwdRules, q, t);
+    // the fused kernel records s in its lane-native layout, for the fused sweep or the 2-pass line adjoint
+    pl.ln_traj = t.s && pl.fwd == ADMM_PATH_FUSED;
     return pl;
 }
 
-// Grouped solve (a PSF, lambda and rho per image or channel): the kernels that take the plane -> group map.
-// 256 x 256 anisotropic from the fused kernel's plane count on: plane256_kernel over per-group lane-native tables;
-// the other tuned shapes (and 256 x 256 below the rule, or isotropic): the 2-pass kernels; every other shape: the
-// runtime-length kernels.  The smooth-length, CU-resident and fused isotropic kernels take one table set only.
-int plan_grouped(int M, int N, bool iso, size_t planes, bool bt) {
-    if (generic_shape(M, N)) return ADMM_PATH_RUNTIME;
-    if (bt) return ADMM_PATH_2PASS;   // ADMM_ISO_PLANE: never the fused kernel
-    const PathIn q{M, N, iso, true, ADMM_MODE_FORWARD, 0, false, false, planes};
-    if (fused_shape(M, N, iso) && fused_enabled() && enough_planes(q, kMinFused)) return ADMM_PATH_FUSED;
-    return iso ? ADMM_PATH_2PASS_ISO : ADMM_PATH_2PASS;
-}
-
-// Grouped adjoint: the recording forward and the reverse sweep of a grouped call (masks and iso_lane stay false).  The
-// fused forward records s only (no dim-2 spectra), so a recording for h_bar takes the 2-pass forward; the sweep is
-// always the 2-pass / runtime-length one, whose kernels take the plane -> group map.
-PathPlan plan_grouped_adjoint(int M, int N, bool iso, bool psf, size_t planes, bool want_h) {
-    PathPlan pl;
-    pl.want_h = want_h && psf;
-    if (generic_shape(M, N)) {
-        pl.fwd = ADMM_PATH_RUNTIME;
-        pl.bwd = iso ? ADMM_PATH_SWEEP_RUNTIME_ISO : ADMM_PATH_SWEEP_RUNTIME;
-        return pl;
+// ---- from a call to its plan ---------------------------------------------------------------------------------------
+PathIn forward_in(const Call& c) {
+    PathIn q{c.M, c.N, iso_batch(c.iso), c.kh > 0, ADMM_MODE_FORWARD, 0, false, false, c.grid_planes(), iso_plane(c.iso), c.kind};
+    // a sharded isotropic solve plans without the plane-count rule: every shard must take the same path, since
+    // the fused and 2-pass kernels hand the reducer their sum maps in different layouts (lane-native float2 vs
+    // natural), and uneven shards can fall on either side of a threshold; so must its recording and its sweep
+    if (c.red) q.planes = 0;
+    // a multi-branch call records from its forward entry; no rho_bar from the ST mask bits, nor from the isotropic
+    // recording (which is the masks trajectory).  Its reverse sweep runs on the grid of its forward (MultiLayout::
+    // two_pass): only the forward of its plan is read.
+    if (c.kind == kMulti && (c.flags & ADMM_MULTI_RECORD)) {
+        q.mode = ADMM_MODE_RECORD;
+        q.rec_flags = (c.flags & ADMM_REC_MASKS) || q.iso ? ADMM_REC_MASKS : 0;
     }
-    const PathIn q{M, N, iso, psf, ADMM_MODE_RECORD, 0, false, false, planes};
-    pl.ln_traj = fused_shape(M, N, iso) && fused_enabled() && !pl.want_h && enough_planes(q, kMinFused);
-    pl.fwd = pl.ln_traj ? ADMM_PATH_FUSED : iso ? ADMM_PATH_2PASS_ISO : ADMM_PATH_2PASS;
-    pl.bwd = iso ? ADMM_PATH_SWEEP_2PASS_ISO : ADMM_PATH_SWEEP_2PASS;
-    return pl;
+    return q;
 }
 
-// Resumable solve (state in and out, residual norms): the kernels that can start from a given s_0.  256 x 256
-// anisotropic from the fused kernel's plane count on: plane256_kernel's state instance (plane_state.hip); the other
-// tuned shapes (and 256 x 256 below the rule, or isotropic): the 2-pass kernels; every other shape: the runtime-length
-// kernels.  The smooth-length, CU-resident and fused isotropic kernels have no state form.
-int plan_state(int M, int N, bool iso, size_t planes) {
-    if (generic_shape(M, N)) return ADMM_PATH_RUNTIME;
-    const PathIn q{M, N, iso, true, ADMM_MODE_FORWARD, 0, false, false, planes};
-    if (fused_shape(M, N, iso) && fused_enabled() && enough_planes(q, kMinFused)) return ADMM_PATH_FUSED;
-    return iso ? ADMM_PATH_2PASS_ISO : ADMM_PATH_2PASS;
+Call shape_call(int M, int N, int P, int B, int kh, int kw, int iso, int maxit) {
+    Call c{};
+    c.M = M, c.N = N, c.P = P, c.B = B, c.kh = kh, c.kw = kw, c.iso = iso, c.maxit = maxit;
+    return c;
+}
+
+PathIn adjoint_in(const Call& c, int phases, int rec_flags, const Grads& g, bool rec_masks) {
+    PathIn q = forward_in(c);
+    q.mode = phases == 3 ? ADMM_MODE_BACKWARD : ADMM_MODE_RECORD;
+    // a replay (phase 2 alone) is planned as the recording it replays was: h_bar as the replay asks (its tag must match
+    // the recording's), masks from the recording's tag
+    q.rec_flags = phases != 2 ? rec_flags : (g.h_bar ? ADMM_REC_HBAR : 0) | (rec_masks ? ADMM_REC_MASKS : 0);
+    q.h_bar = g.h_bar != nullptr, q.rho_bar = g.rho_bar != nullptr;
+    return q;
 }
 
 // lines per block: the largest of 8, 4, 2, 1 dividing N with T * M <= 4096 (LDS ~ 24 T M bytes)
@@ -307,6 +310,20 @@ int admm_get_option(int option, int* value) {
     return ADMM_OK;
 }
 
+// The path queries: validate, map, plan, report.  A query has a shape, a prox, a PSF height and a plane count only.
+static Call query_call(int M, int N, int iso, int kh, CallKind kind) {
+    Call c = shape_call(M, N, 1, 1, kh, kh, iso);
+    c.kind = kind;
+    return c;
+}
+static PathPlan query_plan(const Call& c, long long planes, int mode, int flags, int want_hbar, int want_rho) {
+    float bar = 0.f;   // (stands for a wanted gradient)
+    const Grads g{nullptr, nullptr, want_hbar ? &bar : nullptr, nullptr, want_rho ? &bar : nullptr};
+    PathIn q = mode == ADMM_MODE_FORWARD ? forward_in(c) : adjoint_in(c, mode == ADMM_MODE_BACKWARD ? 3 : 1, flags, g);
+    q.planes = (size_t)planes;   // (given as one count, not as P x B)
+    return plan_paths(q);
+}
+
 int admm_query_paths(int M, int N, int iso, int kh, long long planes, int mode, int flags, int want_hbar, int want_rho,
                      int* fwd_path, int* bwd_path) {
     if (!fwd_path || !bwd_path) return fail(ADMM_E_INVALID, "admm_query_paths: NULL output");
@@ -315,7 +332,7 @@ int admm_query_paths(int M, int N, int iso, int kh, long long planes, int mode, 
     const int rc = check_shape(M, N, 1, 1, kh, kh, iso);
     if (rc) return rc;
     if (planes < 0) return fail(ADMM_E_INVALID, "admm_query_paths: planes must be >= 0");
-    const PathPlan pl = plan_paths(path_in(M, N, iso, kh > 0, mode, flags, want_hbar != 0, want_rho != 0, (size_t)planes));
+    const PathPlan pl = query_plan(query_call(M, N, iso, kh, kSingle), planes, mode, flags, want_hbar, want_rho);
     *fwd_path = pl.fwd;
     *bwd_path = pl.bwd;
     return ADMM_OK;
@@ -327,8 +344,8 @@ int admm_query_forward_schedule(int M, int N, int iso, int kh, long long planes,
     const int rc = check_shape(M, N, 1, 1, kh, kh, iso);
     if (rc) return rc;
     if (planes <= 0) return fail(ADMM_E_INVALID, "admm_query_forward_schedule: planes must be > 0");
-    const PathPlan pl = plan_paths(path_in(M, N, iso, kh > 0, ADMM_MODE_FORWARD, 0, false, false, (size_t)planes));
-    const ChunkPlan cp = forward_chunks(M, N, (size_t)planes, iso_batch(iso), pl.fwd, iso_plane(iso));
+    const Call c = query_call(M, N, iso, kh, kSingle);
+    const ChunkPlan cp = forward_chunks(forward_in(c), query_plan(c, planes, ADMM_MODE_FORWARD, 0, 0, 0), (size_t)planes);
     *chunk_planes = (long long)std::min(cp.chunk, (size_t)planes);
     *streams = cp.streams;
     return ADMM_OK;
@@ -340,13 +357,13 @@ int admm_query_grouped_path(int M, int N, int iso, int kh, long long planes, int
     if (rc) return rc;
     if (planes < 0 || groups < 1 || (planes > 0 && groups > planes))
         return fail(ADMM_E_INVALID, "admm_query_grouped_path: planes must be >= 0 and 1 <= groups <= planes");
-    *fwd_path = plan_grouped(M, N, iso_batch(iso), (size_t)planes, iso_plane(iso));
+    *fwd_path = query_plan(query_call(M, N, iso, kh, kGrouped), planes, ADMM_MODE_FORWARD, 0, 0, 0).fwd;
     return ADMM_OK;
 }
 
 int admm_query_grouped_paths(int M, int N, int iso, int kh, long long planes, int groups, int mode, int flags,
                              int want_hbar, int want_rho, int* fwd_path, int* bwd_path) {
-    (void)want_rho;   // (the grouped sweeps form rho_bar from the same trajectory: it does not change the paths)
+    // (the grouped sweeps form rho_bar from the same trajectory: want_rho does not change the paths)
     if (!fwd_path || !bwd_path) return fail(ADMM_E_INVALID, "admm_query_grouped_paths: NULL output");
     if (mode != ADMM_MODE_FORWARD && mode != ADMM_MODE_RECORD && mode != ADMM_MODE_BACKWARD)
         return fail(ADMM_E_INVALID, "admm_query_grouped_paths: unknown mode %d", mode);
@@ -354,14 +371,8 @@ int admm_query_grouped_paths(int M, int N, int iso, int kh, long long planes, in
     if (rc) return rc;
     if (planes < 0 || groups < 1 || (planes > 0 && groups > planes))
         return fail(ADMM_E_INVALID, "admm_query_grouped_paths: planes must be >= 0 and 1 <= groups <= planes");
-    if (mode == ADMM_MODE_FORWARD) {
-        *fwd_path = plan_grouped(M, N, iso_batch(iso), (size_t)planes, iso_plane(iso));
-        *bwd_path = 0;
-        return ADMM_OK;
-    }
-    if (no_plane_mode(iso, "the grouped adjoint")) return ADMM_E_UNSUPPORTED;
-    const bool want_h = mode == ADMM_MODE_RECORD ? (flags & ADMM_REC_HBAR) != 0 : want_hbar != 0;
-    const PathPlan pl = plan_grouped_adjoint(M, N, iso != 0, kh > 0, (size_t)planes, want_h);
+    if (mode != ADMM_MODE_FORWARD && no_plane_mode(iso, "the grouped adjoint")) return ADMM_E_UNSUPPORTED;
+    const PathPlan pl = query_plan(query_call(M, N, iso, kh, kGrouped), planes, mode, flags, want_hbar, want_rho);
     *fwd_path = pl.fwd;
     *bwd_path = pl.bwd;
     return ADMM_OK;
@@ -374,7 +385,7 @@ int admm_query_state_path(int M, int N, int iso, int kh, long long planes, int* 
     if (planes < 0 || planes > (long long)kChunkPlanes)
         return fail(ADMM_E_INVALID, "admm_query_state_path: planes must be 0 .. %zu", kChunkPlanes);
     if (no_plane_mode(iso, "the state call")) return ADMM_E_UNSUPPORTED;
-    *fwd_path = plan_state(M, N, iso != 0, (size_t)planes);
+    *fwd_path = query_plan(query_call(M, N, iso, kh, kState), planes, ADMM_MODE_FORWARD, 0, 0, 0).fwd;
     return ADMM_OK;
 }
 

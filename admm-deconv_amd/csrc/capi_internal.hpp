@@ -1,11 +1,13 @@
 // capi_internal.hpp -- declarations shared by the library's host translation units:
 //   admm_capi.hip   the extern "C" ABI (include/admm_deconv.h): argument validation, workspace layouts and
 //                   queries, the recordings registry, the profiler API, the output transport (copy / IPC)
-//   admm_paths.hip  the path decision table (plan_paths), the library options and the tile-size policy
+//   admm_paths.hip  the path decision table (plan_paths) with the one mapping from a Call to its input, the path
+//                   queries, the library options and the tile-size policy
 //   admm_launch.hip launch sequencing of the 2-pass / runtime-length / CU-resident / fused paths (the only TU
 //                   that includes the 2-pass kernels): one 2-pass forward and one reverse sweep for every caller,
 //                   one adjoint driver for single and grouped calls
-// A single or grouped call crosses these layers as one Call (and one Grads) by const reference.
+// A call of any family (single, grouped, state, multi-branch) crosses these layers as one Call (and one Grads) by
+// const reference.
 // Reference interface: tvd_fft / tvd_fft_gpu, /root/reference/src/ops/ops.jl:99-188.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -142,12 +144,8 @@ struct ChunkPlan {
     size_t chunk;
     int streams;
 };
-ChunkPlan forward_chunks(int M, int N, size_t planes, bool iso, int fwd_path, bool bt = false);
 // the library's own streams on the current device (created once; non-blocking)
 hipStream_t lib_stream(int i);
-struct PathPlan;
-// forward workspace bytes (one chunk layout, or one per stream of the MALL-resident schedule)
-size_t forward_ws_bytes(int M, int N, size_t planes, int kh, int iso, const PathPlan* pl = nullptr);
 
 // Trajectory recorded by the forward for the backward (all optional).
 struct Traj {
@@ -160,23 +158,32 @@ struct Traj {
 };
 
 // ---- path selection (admm_paths.hip): ONE decision table for every entry point -----------------------------------------------
-// Which kernels a call runs is decided here and nowhere else; run_forward / run_forward_generic / run_backward
-// only execute the plan, and admm_query_paths (include/admm_deconv.h) returns it to tests without a GPU.
-// Inputs: shape, prox, PSF, what the call is (plain forward, recording with ADMM_REC_* flags, combined
-// backward with or without h_bar / rho_bar) and the library options.
+// Which kernels a call runs is decided in plan_paths and nowhere else, for every family; admm_launch.hip only executes
+// the plan, and the admm_query_* entries return it to tests without a GPU.
+// Inputs: shape, prox, PSF, what the call is (plain forward, recording with ADMM_REC_* flags, combined backward with or
+// without h_bar / rho_bar), its family and the library options.  A family does not choose kernels: it states what it
+// asks of them (PathIn::needs), and every rule of the table states what its kernels can take.
+enum CallKind { kSingle, kGrouped, kState, kMulti };
+enum PathCap : unsigned {
+    kCapGroups = 1,     // a plane -> group map (a PSF, lambda and rho per group)
+    kCapState = 2,      // a caller-given s_0
+    kCapPlaneBT = 4,    // ADMM_ISO_PLANE: the block-threshold line kernels
+    kCapBranches = 8,   // several branches in one grid
+};
 struct PathIn {
     int M, N;
     bool iso, psf;
     int mode;            // ADMM_MODE_FORWARD, ADMM_MODE_RECORD, ADMM_MODE_BACKWARD
     int rec_flags;       // ADMM_REC_* (record)
     bool h_bar, rho_bar; // backward: gradients asked for
-    size_t planes;       // P * B of the call (0: unknown, no plane-count rule)
-    bool bt = false;     // ADMM_ISO_PLANE (iso is then false): 2-pass / runtime-length forward and sweep only
+    size_t planes;       // planes of the call's grid (0: unknown or sharded, no plane-count rule)
+    bool bt;             // ADMM_ISO_PLANE (iso is then false)
+    CallKind kind;
+    unsigned needs() const {
+        return (kind == kGrouped ? kCapGroups : kind == kState ? kCapState : kind == kMulti ? kCapBranches : 0u) |
+               (bt ? kCapPlaneBT : 0u);
+    }
 };
-// the plan query of a call's `iso` argument
-inline PathIn path_in(int M, int N, int iso, bool psf, int mode, int rec_flags, bool h_bar, bool rho_bar, size_t planes) {
-    return PathIn{M, N, iso_batch(iso), psf, mode, rec_flags, h_bar, rho_bar, planes, iso_plane(iso)};
-}
 enum MinPlanesFor { kMinFused, kMinFusedIso, kMinResident, kMinResidentIso };
 struct PathPlan {
     bool want_h = false;     // the forward records the dim-2 spectra h_bar needs (2-pass column pass)
@@ -221,7 +228,7 @@ BwdLayout make_bwd_layout(int M, int N, size_t planes, int kh, int kw, int maxit
 struct MultiLayout {
     size_t prm, twM, twN, C, F, hln, sln, traj, sbar, vsl, part, rt, rtmp, total;
     size_t fmap, qpart, nrm, rmap;   // isotropic (ADMM_MULTI_ISO): f maps, q / R partials, |s| slots, R maps
-    // Below the plane-count rule the branches run the 2-pass kernels in one grid (multi_two_pass): spectra, s
+    // Below the plane-count rule the branches run the 2-pass kernels in one grid (two_pass, from the plan): spectra, s
     // state (anisotropic: sA / sbA ping-pong), and for the reverse sweep sbar (two), Vsum and (isotropic) vbar and
     // the plane-group R partials; qpart then holds the plane-group |s|^2 partials, traj / nrm the natural-layout
     // s_k / |s_k| slots (|s_k| per branch), part the (rho_bar, tau_bar) rows of every branch (pbs doubles apart,
@@ -231,12 +238,9 @@ struct MultiLayout {
     int ngb, G, rows_b, nblk_a;
 };
 constexpr int kMultiM = 256, kMultiN = 256;
-// several branches below the fused kernels' plane-count rule run the 2-pass kernels (admm_paths.hip)
-bool multi_two_pass(size_t planes, int flags);
 size_t multi_C_bytes();
 size_t multi_F_bytes();
 size_t multi_iso_rows(int K);
-admm::plane::Branches multi_branches(int P, int B, int nbr);
 
 // ---- resumable solve (admm_tvd_forward_state_dev_f32) ----
 // What a state call reads and writes besides y and x_out (null: not given / not wanted), and its own workspace slots
@@ -253,8 +257,8 @@ struct StateIO {
 };
 
 // ---- the call descriptor ----
-// What a solve is.  Every extern "C" entry point of the single and the grouped family fills one in once, and
-// everything below the ABI receives it by const reference.
+// What a solve is.  Every extern "C" entry point fills one in once (the shape-only workspace and path queries with the
+// fields they have), and everything below the ABI receives it by const reference.
 struct Call {
     const float* y;
     float* x_out;
@@ -268,16 +272,36 @@ struct Call {
     void* stream;
     const admm_batch_reducer* red;   // the batch reducer, only where it acts: isotropic and fn set
     int gb = 1, gp = 1, nparam = 1;  // the grouping (admm_tvd_*_grouped_*); a single solve: one group, one pair
-    bool grouped = false;
+    CallKind kind = kSingle;         // the family: what the call asks of its kernels (PathIn::needs)
     const StateIO* st = nullptr;     // a state call: never the smooth-length kernels, warm start when st->in is set
-    size_t planes() const { return (size_t)P * B; }
+    // a multi-branch call (admm_tvd_*_multi_*): nbranch solves of the same P x B planes in one grid, branch i with the
+    // device scalars lam_b[i] / rho_b[i] (host arrays; sc is not used), its ADMM_MULTI_* / ADMM_REC_* flags
+    int nbranch = 1;
+    const float* const* lam_b = nullptr;
+    const float* const* rho_b = nullptr;
+    int flags = 0;
+    bool grouped() const { return kind == kGrouped; }
+    size_t planes() const { return (size_t)P * B; }              // input planes
+    size_t grid_planes() const { return planes() * nbranch; }    // planes solved: every branch's
     int groups() const { return gb * gp; }
 };
-// What an adjoint reads (x_bar) and writes (null: not wanted); all null for a recording forward.
+// What an adjoint reads (x_bar) and writes (null: not wanted); all null for a recording forward.  lambda_bar / rho_bar:
+// one value per (lambda, rho) pair of the call -- nparam of a grouped call, nbranch of a multi-branch one.
 struct Grads {
     const float* x_bar;
     float *y_bar, *h_bar, *lambda_bar, *rho_bar;
 };
+
+// ---- from a call to its plan (admm_paths.hip) ----
+// The one mapping from a Call to the decision table's input, per direction; every solve, workspace size and path query
+// goes through it, so the three take the same plan.  forward_in: a plain forward (a multi-branch call: its forward with
+// or without ADMM_MULTI_RECORD).  adjoint_in: phases as run_backward's (1 recording, 2 replay, 3 combined), rec_flags
+// the recording's request, g the gradients asked for, rec_masks the masks flag of the recording a replay found.
+Call shape_call(int M, int N, int P, int B, int kh, int kw, int iso, int maxit = 0);   // a shape-only entry's Call
+PathIn forward_in(const Call& c);
+PathIn adjoint_in(const Call& c, int phases, int rec_flags, const Grads& g, bool rec_masks = false);
+// the chunk schedule of a forward of `planes` planes planned as pl (q.planes is 0 for a sharded call)
+ChunkPlan forward_chunks(const PathIn& q, const PathPlan& pl, size_t planes);
 
 // ---- workspace carving ----
 struct Carver {
@@ -290,10 +314,8 @@ struct Carver {
 };
 
 // ---- grouped solve (admm_tvd_forward_grouped_dev_f32) ----
-// One path decision (admm_paths.hip): the fused kernel at 256 x 256 anisotropic from the plane-count rule, the
-// 2-pass kernels at the other tuned shapes, the runtime-length kernels elsewhere (never the smooth-length, resident
-// or fused isotropic kernels, never the MALL chunk schedule).
-int plan_grouped(int M, int N, bool iso, size_t planes, bool bt = false);
+// Planned by plan_paths on the rules whose kernels take the plane -> group map (kCapGroups); one launch sequence over
+// the whole batch, never the MALL chunk schedule.
 // floats (C) / float2 (G) between the groups' 2-pass tables
 inline unsigned group_tab_f(int M, int N) { return (unsigned)(align_up((size_t)(M / 2 + 1) * N * 4) / 4); }
 // Workspace: the single-PSF forward layout of the whole batch, and behind it G consecutive blocks of each table
@@ -303,12 +325,8 @@ inline unsigned group_tab_f(int M, int N) { return (unsigned)(align_up((size_t)(
 Layout make_grouped_layout(int M, int N, size_t planes, int groups, bool psf, bool iso);
 
 // ---- grouped adjoint (admm_tvd_backward_grouped_*) ----
-// One path decision (admm_paths.hip), reported by admm_query_grouped_paths: runtime-length shapes record with the
-// runtime-length forward and sweep with sweep_runtime(_iso); 256 x 256 anisotropic from the plane-count rule, fused
-// enabled and no h_bar trajectory records lane-native s with the fused forward and sweeps with sweep_2pass (ln_traj);
-// everything else is the 2-pass forward and sweep_2pass(_iso).  Never the fused reverse sweeps (one table set), the
-// smooth-length or resident kernels, or the MALL chunk schedule: masks and iso_lane stay false.
-PathPlan plan_grouped_adjoint(int M, int N, bool iso, bool psf, size_t planes, bool want_h);
+// Planned by plan_paths too (reported by admm_query_grouped_paths): no fused reverse sweep takes the group map, so masks
+// and iso_lane stay false and a fused forward's lane-native trajectory (ln_traj) is swept by sweep_2pass.
 // Workspace: a BwdLayout of the whole batch, behind it the grouped table blocks of make_grouped_layout and, per group,
 // sig (PSF spectrum), Q, hcorr, hA and rt; f.prm / C / G / F and sig / Q / hcorr / hA / rt name those blocks (the
 // layout's own single-set slots stay allocated and unused).  gtmp: the split partials of the group-segmented sums.
@@ -319,12 +337,9 @@ inline int group_split(long long n) {
     return p < 1 ? 1 : p > 256 ? 256 : (int)p;
 }
 
-// ---- resumable solve: path and workspace ----
-// One path decision (admm_paths.hip), reported by admm_query_state_path: the fused kernel's state instance at 256 x 256
-// anisotropic from the fused kernel's plane count, the 2-pass kernels at the other tuned power-of-two shapes (and at
-// 256 x 256 isotropic or below the plane-count rule), the runtime-length kernels elsewhere, both proxes.  Never the
-// smooth-length, CU-resident or fused isotropic kernels, never the MALL chunk schedule: those take no s_0.
-int plan_state(int M, int N, bool iso, size_t planes);
+// ---- resumable solve: workspace ----
+// Planned by plan_paths on the rules whose kernels can start from a given s_0 (kCapState; reported by
+// admm_query_state_path); one launch sequence over the whole batch.
 // Workspace: the forward layout of the whole batch, then v_0, the factor map of s_K (isotropic), the residual block
 // sums and (256 x 256 anisotropic) a natural-layout s_K for a fused call that wants residuals without state_out.
 struct StateLayout {
@@ -338,7 +353,7 @@ StateLayout make_state_layout(int M, int N, size_t planes, bool psf, bool iso);
 // once (two_pass_forward / two_pass_reverse on a TwoPass grid: a single or grouped solve, or the one-grid call's
 // branches), as do the isotropic norm step, the fused isotropic loops and the gradient assembly.
 // run_forward: np planes of the call from plane p0 on (default: all of them), through the layout `lay` at `ws`.  A
-// grouped call (c.grouped): h holds one PSF per group, sc.lam / sc.rho point at nparam device values, lay is
+// grouped call (c.grouped()): h holds one PSF per group, sc.lam / sc.rho point at nparam device values, lay is
 // make_grouped_layout's (or a grouped BwdLayout's f); the setup kernels run over the groups.
 // tables = false: the workspace already holds this call's twiddles, C / G tables and scalar block (a later plane
 // chunk of the same call through the same chunk workspace): the setup kernels are not launched again
@@ -349,11 +364,9 @@ int run_forward(Launcher& ln, const Call& c, unsigned char* ws, const Layout& la
 int launch_backward(int phases, const Call& c, const Grads& g, const PathPlan& plan, const BwdLayout& bl);
 // a state call (c.st set): the forward on `path` from s_0 or the zero state, then the end kernels (s_K, residual norms)
 int launch_forward_state(const Call& c, const StateLayout& L, int path);
-int launch_forward_multi(const float* y, float* x_out, int M, int N, int P, int B, int nbr, const float* const* lambda,
-                         const float* const* rho, int maxit, int flags, void* workspace, void* stream, size_t planes,
-                         const MultiLayout& L);
-int launch_backward_multi(const float* x_bar, float* y_bar, float* lambda_bar, float* rho_bar, int M, int N, int P,
-                          int B, int nbr, int maxit, const float* x_out, void* workspace, void* stream, int flags,
-                          size_t planes, size_t ppb, size_t MN, const MultiLayout& L);
+// a multi-branch call on the grid its layout was planned for (L.two_pass): the forward (recording with
+// ADMM_MULTI_RECORD in c.flags), and the reverse sweep of such a recording (c.x_out: the recorded forward's output)
+int launch_forward_multi(const Call& c, const MultiLayout& L);
+int launch_backward_multi(const Call& c, const Grads& g, const MultiLayout& L);
 
 }  // namespace admm_capi

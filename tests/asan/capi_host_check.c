@@ -93,6 +93,64 @@ static void validation(void) {
     CHECK(strlen(admm_last_error()) < 4096);
 }
 
+/* The multi-branch family: every refusal of its three entry points before any device work (the sweep of
+ * tests/golden/gen_path_decisions.py), through the call descriptor's branch count, per-branch scalar arrays and flags. */
+static void multi_validation(void) {
+    char* fake = (char*)(1 << 20);   /* never dereferenced: every call below fails validation first */
+    float *f = (float*)fake, *odd = (float*)(fake + 4);
+    const float* dev[2] = {f, f};
+    const float* hole[2] = {f, NULL};
+    const size_t big = (size_t)1 << 40;
+    size_t ws = 0, ws2 = 0;
+    /* sizes on both sides of the plane-count rule (96 planes anisotropic): the two grids' layouts */
+    CHECK(admm_tvd_multi_workspace_bytes(256, 256, 1, 19, 5, 50, ADMM_MULTI_RECORD, &ws) == ADMM_OK && ws > 0);
+    CHECK(admm_tvd_multi_workspace_bytes(256, 256, 3, 16, 2, 50, ADMM_MULTI_RECORD, &ws2) == ADMM_OK && ws2 > 0);
+    CHECK(admm_tvd_multi_workspace_bytes(256, 256, 3, 2, 2, 5, ADMM_MULTI_ISO, &ws) == ADMM_OK && ws > 0);
+    CHECK(admm_tvd_multi_workspace_bytes(256, 256, 3, 2, 2, 5, 0, NULL) == ADMM_E_INVALID);
+    CHECK(admm_tvd_multi_workspace_bytes(256, 256, 0, 2, 2, 5, 0, &ws) == ADMM_E_INVALID);
+    CHECK(admm_tvd_multi_workspace_bytes(256, 256, 3, 2, 2, 5, 8, &ws) == ADMM_E_INVALID);
+    CHECK(admm_tvd_multi_workspace_bytes(128, 256, 3, 2, 2, 5, 0, &ws) == ADMM_E_UNSUPPORTED);
+    CHECK(admm_tvd_multi_workspace_bytes(256, 256, 3, 4353, 5, 5, 0, &ws) == ADMM_E_UNSUPPORTED);
+#define FWD(y, x, M, nbr, lam, rho, maxit, flags, w, bytes) \
+    admm_tvd_forward_multi_dev_f32(y, x, M, 256, 3, 2, nbr, lam, rho, maxit, flags, w, bytes, NULL)
+    CHECK(FWD(f, f, 256, 0, dev, dev, 5, 0, fake, big) == ADMM_E_INVALID);
+    CHECK(FWD(f, f, 256, 2, dev, dev, -1, 0, fake, big) == ADMM_E_INVALID);
+    CHECK(FWD(f, f, 256, 2, dev, dev, 5, 8, fake, big) == ADMM_E_INVALID);
+    CHECK(FWD(f, f, 128, 2, dev, dev, 5, 0, fake, big) == ADMM_E_UNSUPPORTED);
+    CHECK(FWD(NULL, f, 256, 2, dev, dev, 5, 0, fake, big) == ADMM_E_INVALID);
+    CHECK(FWD(f, NULL, 256, 2, dev, dev, 5, 0, fake, big) == ADMM_E_INVALID);
+    CHECK(FWD(odd, f, 256, 2, dev, dev, 5, 0, fake, big) == ADMM_E_INVALID);
+    CHECK(FWD(f, odd, 256, 2, dev, dev, 5, 0, fake, big) == ADMM_E_INVALID);
+    CHECK(FWD(f, f, 256, 2, NULL, dev, 5, 0, fake, big) == ADMM_E_INVALID);
+    CHECK(FWD(f, f, 256, 2, dev, NULL, 5, 0, fake, big) == ADMM_E_INVALID);
+    CHECK(FWD(f, f, 256, 2, hole, dev, 5, 0, fake, big) == ADMM_E_INVALID);
+    CHECK(strstr(admm_last_error(), "lambda[1]") != NULL);
+    CHECK(FWD(f, f, 256, 2, dev, hole, 5, 0, fake, big) == ADMM_E_INVALID);
+    CHECK(FWD(f, f, 256, 2, dev, dev, 5, 0, NULL, big) == ADMM_E_WORKSPACE);
+    CHECK(FWD(f, f, 256, 2, dev, dev, 5, ADMM_MULTI_RECORD | ADMM_MULTI_ISO, fake, 16) == ADMM_E_WORKSPACE);
+    CHECK(FWD(f, f, 256, 2, dev, dev, 5, 0, fake + 16, big) == ADMM_E_WORKSPACE);
+    /* wrong in several ways: the checks fire in a fixed order */
+    CHECK(FWD(NULL, f, 128, 2, NULL, dev, 5, 8, NULL, 0) == ADMM_E_INVALID);
+    CHECK(strstr(admm_last_error(), "unknown flags") != NULL);
+    CHECK(FWD(f, odd, 256, 2, hole, dev, 5, 0, fake, 16) == ADMM_E_INVALID);
+    CHECK(strstr(admm_last_error(), "16-byte aligned") != NULL);
+#undef FWD
+#define BWD(xb, yb, M, B, xo, w) \
+    admm_tvd_backward_multi_recorded_dev_f32(xb, yb, NULL, NULL, M, 256, 3, B, 2, 5, xo, w, big, NULL)
+    CHECK(BWD(f, f, 256, 0, f, fake) == ADMM_E_INVALID);
+    CHECK(BWD(f, f, 128, 2, f, fake) == ADMM_E_UNSUPPORTED);
+    CHECK(BWD(NULL, f, 256, 2, f, fake) == ADMM_E_INVALID);
+    CHECK(BWD(f, f, 256, 2, NULL, fake) == ADMM_E_INVALID);
+    CHECK(BWD(odd, f, 256, 2, f, fake) == ADMM_E_INVALID);
+    CHECK(BWD(f, odd, 256, 2, f, fake) == ADMM_E_INVALID);
+    /* a replay on a workspace that holds no recording */
+    CHECK(BWD(f, NULL, 256, 2, f, fake + 512) == ADMM_E_INVALID);
+    CHECK(strstr(admm_last_error(), "no multi-branch recording of 2 branches") != NULL);
+    CHECK(BWD(odd, f, 256, 2, f, fake + 512) == ADMM_E_INVALID);
+    CHECK(strstr(admm_last_error(), "16-byte aligned") != NULL);
+#undef BWD
+}
+
 static void options_and_profiler(void) {
     int v = -1;
     for (int o = 0; o < ADMM_OPT_COUNT; ++o) CHECK(admm_get_option(o, &v) == ADMM_OK);
@@ -113,6 +171,7 @@ int main(void) {
     CHECK(admm_abi_version() == ADMM_ABI_VERSION);
     sizes();
     validation();
+    multi_validation();
     options_and_profiler();
     if (failures) {
         fprintf(stderr, "%d check(s) failed\n", failures);

@@ -1,5 +1,5 @@
 """The path every (shape, prox, PSF, call, record flags, options) combination must take -- the expected side of
-admm_query_paths (admm_capi.hip plan_paths, the library's one decision table).  Shared by the CPU test
+admm_query_paths (admm_paths.hip plan_paths, the library's one decision table).  Shared by the CPU test
 (tests/test_capi.py: the table against the query) and the GPU test (tests/test_gpu_paths.py: the kernels that
 actually launch against the table).  mode: 0 forward, 1 record (flags = ADMM_REC_*), 2 combined backward."""
 
